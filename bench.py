@@ -16,12 +16,14 @@ Trials shard across ranks with no other exchange (weak scaling: 1000 trials per 
                                              has fewer than N GPUs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
-Rank 0 prints ONE JSON line, kept under 4 KB: headline, `roofline` (K4h), `selfcheck` (the timed launch against
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline only (`value`,
+`ms_per_step`, `dtype`, the configuration); `--dump-outputs DIR` also writes the coherence of the last timed step.
+With `--full` the line, kept under 4 KB, also carries `roofline` (K4h), `selfcheck` (the timed launch against
 complex128), at N = 1 also the twins of the headline at the reference's operand precision (`value_f32_products`,
 `value_reference_arithmetic`), a compact `secondary` (c2 mtmfft power, other trial lengths, c4 sliding-window FFT and
 Morlet wavelets, the front-end- and host-copy-inclusive headline, c5 Wilson / Granger) and a compact `cpu_baseline`
 (the oracle on the host cores: BASELINE.md section 4.2).  Everything longer - the full secondary entries with kernel
-names, bounds and counter provenance, notes, the CPU-baseline variants - goes to gpurun_out/bench_detail.json.
+names, bounds and counter provenance, notes, the CPU-baseline variants - goes to the detail file (DETAIL_FILE).
 """
 import argparse
 import json
@@ -58,9 +60,37 @@ def parse():
                     help="FFT -> CSD hand-over in the channel-blocked layout (faster FFT stores, slower CSD fetch)")
     ap.add_argument("--no-reference-mean", action="store_true",
                     help="detrend with float64 block sums instead of the reference's float32 row-order mean (A/B)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the c2 / c4 / c5 secondary measurements")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, latency, selfcheck, the twins at the reference's precision, "
+                         "secondary and cpu_baseline, with the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the coherence of the last timed step to DIR (float32 .npy, a seeded sample of its rows "
+                         "when the whole array exceeds %d MB)" % (DUMP_BYTES >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the c2 / c4 / c5 secondary measurements")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 48 << 20
+
+
+def dump_outputs(path, coh):
+    """--dump-outputs: what the timed path returns, the (F, C, C) float32 coherence of its last step.  Written whole as
+    coherence.npy when it fits in DUMP_BYTES, else as coherence_rows.npy: the rows coh[f, i, :] at a fixed seeded choice
+    of flat indices f * C + i, in ascending order (the same rows for the same arguments)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    F, C = coh.shape[0], coh.shape[1]
+    if coh.numel() * 4 <= DUMP_BYTES:
+        np.save(os.path.join(path, "coherence.npy"), coh.cpu().numpy().astype(np.float32, copy=False))
+        return
+    nrows = max(1, min(F * C, DUMP_BYTES // (4 * C)))
+    idx = np.sort(np.random.default_rng(0).choice(F * C, size=nrows, replace=False))
+    rows = coh.reshape(F * C, C).index_select(0, torch.from_numpy(idx).to(coh.device))
+    np.save(os.path.join(path, "coherence_rows.npy"), rows.cpu().numpy().astype(np.float32, copy=False))
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -832,13 +862,50 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        coh = step(rec_main)
+        coh = step(rec_main if args.full else None)      # per-kernel events only where the roofline reads them
     fence()
     el = time.perf_counter() - t0
     tmax = torch.tensor([el], device="cuda", dtype=torch.float64)
     if dist_on:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     el = float(tmax.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, coh)
+
+    k4h = C == 256 and not blocked and not os.environ.get("SPYHIP_CSD_F32")
+    value = world * T * args.steps / el
+    step_ms = 1e3 * el / args.steps
+
+    def headline(coll):
+        return {
+            "metric": "trials/sec for mtmfft+coherence (256 ch x 4096 samples, 7 DPSS tapers, full CSD)",
+            "value": value,
+            "unit": "trials/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": step_ms,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32 transforms; CSD operands fp16 hi+lo (22-bit), f32 accumulate" if k4h else "f32",
+            "data": "synthetic",
+            "config": {
+                "workload": "BASELINE configs[2]: connectivityanalysis method='coh', AR(2) AnalogData, "
+                            f"{C} ch x {N} samp x {T} trials per GPU, tapsmofrq=1 Hz ({K} DPSS tapers), polyremoval=0, "
+                            "output='abs', inputs resident in HBM",
+                "trials_per_gpu": T, "channels": C, "samples": N, "tapers": K, "freqs": F, "batch": B,
+                "fft_kernel": plan.kernel_name + (" + seq_mean_kernel" if refmean else ""),
+                "collective": {"executed": bool(dist_on), "bytes": coll.get("bytes"), "ms": coll.get("pack_allreduce_unpack_ms")},
+            },
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(_short(headline({}), 5), separators=(",", ":")), flush=True)
+        if dist_on:
+            close_group(torch, dist, be)
+        return
 
     # one more analysis, fenced on both sides: the un-pipelined latency of a single analysis (the timed steps above
     # overlap the collective / coherence tail of step i with the transforms of step i + 1 when N > 1)
@@ -910,13 +977,11 @@ def main():
         executed = ((rows[0] + 3) // 4) * F * nsub * 3 * 2048.0 if is3m else None
         # K4h (256 channels, standard layout): 12 v_mfma_f32_16x16x32_f16 (16384 flop) per 16 x 16 sub-tile and chunk of 32
         # rows on the frequencies of the full rounds of workgroups; the frequencies beyond them run the float32 tail
-        k4h = C == 256 and not blocked and not os.environ.get("SPYHIP_CSD_F32")
         if k4h:
             ncu = torch.cuda.get_device_properties(0).multi_processor_count
             rem = F % ncu
             f_main = F - rem if (F > ncu and 0 < rem and 4 * rem <= ncu) else F
             executed = ((rows[0] + 31) // 32) * f_main * 136 * 12 * 16384.0
-        value = world * T * args.steps / el
         coll = {"executed": bool(dist_on), "backend": None}
         if dist_on:
             coll["backend"] = ("RCCL through torch.distributed (the library's communicator could not be created on every rank)"
@@ -964,7 +1029,6 @@ def main():
                         "Hermitian-minimal triangle)", "traffic_source": traffic_prov}
         # the whole step against the bytes SURVEY 8(d) counts for it (input once, accumulator once) and against what the
         # two-kernel formulation moves (spectra written by K1 and read by K4)
-        step_ms = 1e3 * el / args.steps
         alg_step = T * N * C * 4 + F * C * C * 8
         form_step = T * (N * C * 4 + 2 * K * F * C * 8) + 2 * F * C * C * 8
         step_info = {"fft_ms": sum(fft_ms) / args.steps, "csd_ms": sum(csd_ms) / args.steps,
@@ -974,32 +1038,13 @@ def main():
         if coll.get("pack_allreduce_unpack_ms"):
             step_info["allreduce_ms"] = coll["pack_allreduce_unpack_ms"]
             step_info["allreduce_GB"] = coll["bytes"] / 1e9
-        line = {
-            "metric": "trials/sec for mtmfft+coherence (256 ch x 4096 samples, 7 DPSS tapers, full CSD)",
-            "value": value,
-            "unit": "trials/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": step_ms,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32 transforms; CSD operands fp16 hi+lo (22-bit), f32 accumulate" if k4h else "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": "BASELINE configs[2]: connectivityanalysis method='coh', AR(2) AnalogData, "
-                            f"{C} ch x {N} samp x {T} trials per GPU, tapsmofrq=1 Hz ({K} DPSS tapers), polyremoval=0, "
-                            "output='abs', inputs resident in HBM",
-                "trials_per_gpu": T, "channels": C, "samples": N, "tapers": K, "freqs": F, "batch": B,
-                "fft_kernel": plan.kernel_name + (" + seq_mean_kernel" if refmean else ""),
-                "collective": {"executed": bool(dist_on), "bytes": coll.get("bytes"), "ms": coll.get("pack_allreduce_unpack_ms")},
-            },
+        line = headline(coll)
+        line.update({
             "roofline": roofline,
             "step": step_info,
             "analysis_latency_ms": 1e3 * latency,
             "selfcheck": selfcheck,
-        }
+        })
         detail = {"line": None, "roofline_notes": roofline_notes, "collective": coll, "twins": twins,
                   "selfcheck_criterion": "|a-b| <= 1e-5 |b| + 1e-6 max|b| against complex128 / float64 references of the same inputs; frequencies %s" % fsel,
                   "headline_frac_vs_survey_bound": value / (world * HEADLINE_BOUND_TRIALS_PER_S),
@@ -1037,9 +1082,13 @@ def main():
         detail["line"] = dict(line)
         emit(line, detail)
     if dist_on:
-        torch.cuda.synchronize()
-        be.shutdown_library_comm()
-        dist.destroy_process_group()
+        close_group(torch, dist, be)
+
+
+def close_group(torch, dist, be):
+    torch.cuda.synchronize()
+    be.shutdown_library_comm()
+    dist.destroy_process_group()
 
 
 if __name__ == "__main__":

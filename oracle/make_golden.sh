@@ -18,6 +18,13 @@ if [ "${1:-}" = "--container" ]; then      # the .spy container fixtures (tests/
     /opt/conda/bin/python3.9 -W ignore "$here/oracle/gen_spy_container.py" "$here/tests/golden/spy_container"
   exit 0
 fi
+if [ "${1:-}" = "--egress" ]; then           # tests/golden/spy_container/egress.spy: written here, then loaded by the reference
+  cont="$here/tests/golden/spy_container/egress.spy"
+  rm -rf "$cont"
+  python "$here/oracle/gen_egress_container.py" "$cont"
+  bash "$here/oracle/make_golden.sh" --check-container "$cont"
+  exit 0
+fi
 if [ "${1:-}" = "--check-container" ]; then   # load a container written by syncopy_amd.io.save with the reference
   SPYDIR="$tmp/spydir" SPYSILENTSTARTUP=1 SPYLOGLEVEL=ERROR PYTHONPATH="$tmp/stubs:/root/reference" \
     /opt/conda/bin/python3.9 -W ignore "$here/oracle/gen_spy_container.py" --check "$2"

@@ -75,3 +75,30 @@ def test_final_line_stays_under_4k(tmp_path, monkeypatch, capsys):
     assert got["roofline"]["frac"] == 0.5 and got["cpu_baseline"]["cores"] == 1 and "secondary" not in got
     detail = json.load(open(os.path.join(str(tmp_path), got["detail"])))
     assert len(detail["secondary"]) == 20
+
+
+def test_steps_below_one_are_refused():
+    p = _run(["--gpus", "1", "--steps", "0"], SPY_BENCH_LAUNCH_TEST="1")
+    assert p.returncode == 2 and "{" not in p.stdout and "--steps" in p.stderr
+
+
+def test_dump_outputs_whole_or_seeded_rows(tmp_path, monkeypatch):
+    """--dump-outputs: the coherence whole when it fits, else the same seeded rows on every call, within DUMP_BYTES."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    coh = torch.rand((33, 16, 16), generator=torch.Generator().manual_seed(3))
+    bench.dump_outputs(str(tmp_path / "whole"), coh)
+    assert os.listdir(tmp_path / "whole") == ["coherence.npy"]
+    got = np.load(tmp_path / "whole" / "coherence.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, coh.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * 16 * 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), coh)
+        assert os.listdir(tmp_path / d) == ["coherence_rows.npy"]
+    a, b = np.load(tmp_path / "a" / "coherence_rows.npy"), np.load(tmp_path / "b" / "coherence_rows.npy")
+    assert a.dtype == np.float32 and a.shape == (100, 16) and np.array_equal(a, b)
+    flat = coh.numpy().reshape(-1, 16)
+    assert all(any(np.array_equal(r, f) for f in flat) for r in a)                  # whole rows of the array
+    assert (tmp_path / "a" / "coherence_rows.npy").stat().st_size <= 100 * 16 * 4 + 256

@@ -102,7 +102,7 @@ def test_bench_distributed_branch():
     """bench.py exactly as the driver launches it for N > 1 (torch.distributed.run, nccl), on the GPUs present."""
     n = min(_ngpu(), 2)
     r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--trials", "60",
-                 "--no-cpu-baseline", "--no-secondary"], n, {"SPY_BENCH_FORCE_DIST": "1"})
+                 "--full", "--no-cpu-baseline", "--no-secondary"], n, {"SPY_BENCH_FORCE_DIST": "1"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

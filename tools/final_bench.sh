@@ -2,7 +2,7 @@
 # ONE script behind every figure of the bench line (VERDICT r3 "next" 3).  On the GPU box:  bash tools/final_bench.sh
 # Everything lands in gpurun_out/final/ (summaries only: traces stay in /tmp); the files are then copied to profiles/r6_*
 # (bench.py: PROFILE_ROUND).
-#   bench.json, bench_detail.json   python bench.py --steps 20 --warmup 5 (the line the driver also produces, and the detail file behind it)
+#   bench.json, bench_detail.json   python bench.py --steps 20 --warmup 5 --full (the full line and the detail file behind it)
 #   bench_kernel_stats.csv          rocprofv3 --kernel-trace --stats of the headline-only run (K0 / K1 / K4 / K5 rows)
 #   bench_under_rocprof.json        that run's own line (HIP-event averages inside the profiled process)
 #   secondary_kernel_stats.txt      rocprofv3 --kernel-trace --stats of each `secondary` workload through the torch-free
@@ -39,13 +39,13 @@ for m in $MODES; do
 done
 grep -E "^##|^\"spy" $O/secondary_kernel_stats.txt | cut -c1-150
 cp $O/pmc_secondary.txt profiles/r6_pmc_secondary.txt
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 cp gpurun_out/bench_detail.json $O/bench_detail.json
 tail -c 400 $O/bench.err
 echo "bench line: $(wc -c < $O/bench.json) bytes"
 cd /tmp
 rm -rf /tmp/prof_bench
-rocprofv3 --kernel-trace --stats -d /tmp/prof_bench -o p --output-format csv -- python $R/bench.py --no-secondary --no-cpu-baseline > $O/bench_under_rocprof.json 2> /tmp/rocprof_bench.err
+rocprofv3 --kernel-trace --stats -d $TMPDIR/prof_bench -o p --output-format csv -- python $R/bench.py --full --no-secondary --no-cpu-baseline > $O/bench_under_rocprof.json 2> $TMPDIR/rocprof_bench.err
 f=$(find /tmp/prof_bench -name "*kernel_stats.csv" | head -1)
 grep -E "^\"Name\"|spy" "$f" > $O/bench_kernel_stats.csv
 head -6 $O/bench_kernel_stats.csv | cut -c1-170
