@@ -354,9 +354,11 @@ int spyhip_cwt_plan_destroy(spyhip_cwt_plan* plan);
  * kernels (~5e-7 of a trial's largest coefficient). */
 int spyhip_cwt_plan_set_precision(spyhip_cwt_plan* plan, int reference);
 /* on = 1 (default): scales whose kernel support fits 1024- / 2048-point blocks leave their transform kernel in the output's
- * own (segment, time, scale, channel) layout (cwt2d_kernel: 16 / 8 channels per workgroup, 64- / 32-byte runs); trial sums
- * (accumulate = 2) are read-modify-writes of tiles a workgroup owns.  0: every scale through the time-contiguous staging
- * buffer and the transposition pass (rounds 1-5; kept for A/B measurements and as the cross-check of the direct kernels).
+ * own (segment, time, scale, channel) layout (cwt2d_kernel: 16 / 8 channels per workgroup, 64- / 32-byte runs) for
+ * accumulate = 0 / 1; trial sums (accumulate = 2) and float64 precision always go through the staging buffer.  Plans whose
+ * time slots do not increase with the samples, or whose tiles' slots span 4 GiB or more of the output (gapped tpos), are
+ * staged only: on = 1 fails for them (-3).  0: every scale through the time-contiguous staging buffer and the
+ * transposition pass (rounds 1-5; kept for A/B measurements and as the cross-check of the direct kernels).
  * Replaces the (nScales, N, C) array the reference writes once per trial: specest/wavelets/transform.py:88-108. */
 int spyhip_cwt_plan_set_direct(spyhip_cwt_plan* plan, int on);
 /* seg_start_d: row of sample 0 of each pre-selected signal; trial_lo_d/trial_hi_d: rows of the

@@ -42,7 +42,7 @@ struct spyhip_cwt_plan {
     size_t stage_cap = 0;         // its size in bytes
     int chunk = 0;                // segments per chunk the staging buffer holds
     bool direct = true;           // spyhip_cwt_plan_set_direct: groups flagged `direct` skip the staging buffer
-    bool direct_ok = true;        // what plan creation decided (slots increasing, 32-bit row offsets)
+    bool direct_ok = true;        // what plan creation decided (cwt_direct_fits: slots increasing, 32-bit tile offsets)
     std::vector<int> staged;      // scales that still go through it (blocks of 4096 points and more), in staging-row order
     spy::DevBuf<int> smap;        // staging row -> scale index (device copy of `staged`)
     spy::DevBuf<int> lidx_stage;  // long scale -> staging row
@@ -379,20 +379,24 @@ static int cwt_plan_create_impl(spyhip_ctx* ctx, int nsig, int nchan, int nscale
         for (int v : tp)
             if (v >= ntime_out) { spy::set_error("cwt_plan_create: tpos entry %d >= ntime_out %d", v, ntime_out); delete p; return -1; }
         if (p->tpos.upload(tp, ctx->stream)) { delete p; return -2; }
-        // the direct kernels address a tile relative to the slot reached before it: slots must increase with the samples
+        // the direct kernels address a tile relative to the slot reached before it (cwt_direct_fits)
         std::vector<int> fl(nsig);
         int last = -1;
         for (int n = 0; n < nsig; ++n) {
-            if (tp[n] >= 0) {
-                if (tp[n] <= last) p->direct = false;
-                last = tp[n];
-            }
+            if (tp[n] >= 0) last = tp[n];
             fl[n] = std::max(last, 0);
         }
         if (p->tfloor.upload(fl, ctx->stream)) { delete p; return -2; }
     }
-    // ... and a block's rows must stay within 32-bit byte offsets
-    if ((double)p->nscales * p->nchan * 8.0 * 2048.0 >= 4294967296.0) p->direct = false;
+    // slots increasing with the samples, and every tile's stores within 32-bit byte offsets of its reference slot
+    {
+        std::vector<int> vd;
+        for (const CwtGroup* g : p->groups)
+            if (g->direct) vd.push_back(g->V);
+        const unsigned long long esz = output == SPYHIP_OUT_FOURIER ? 8 : 4;
+        const unsigned long long chanb = (unsigned long long)nchan * esz, rowb = (unsigned long long)nscales * chanb;
+        if (!vd.empty() && !spyfft::cwt_direct_fits(tpos, nsig, vd.data(), (int)vd.size(), rowb, chanb)) p->direct = false;
+    }
     p->direct_ok = p->direct;
     *out = p;
     return 0;
@@ -638,9 +642,9 @@ extern "C" int spyhip_cwt_exec(spyhip_cwt_plan* p, const float* data_d, int64_t 
 
 extern "C" int spyhip_cwt_plan_set_direct(spyhip_cwt_plan* p, int on) {
     if (!p) { spy::set_error("cwt_plan_set_direct: null plan"); return -1; }
-    if (on && !p->direct_ok) {                   // (slots not increasing / rows beyond 32-bit offsets: staging only)
+    if (on && !p->direct_ok) {                   // (slots not increasing / tiles beyond 32-bit offsets: staging only)
         spy::set_error("cwt_plan_set_direct: this plan's outputs cannot be written by the transform kernels (time slots not "
-                       "increasing with the samples, or rows beyond 32-bit offsets)");
+                       "increasing with the samples, or a tile's slots spanning 4 GiB or more of the output)");
         return -3;
     }
     p->direct = on != 0;

@@ -486,10 +486,10 @@ def cwt_plan_tables(nsig, scales, dt, w0, nbmin=1024):
 
 
 def cwt_exec(data, seg_start, trial_lo, trial_hi, nsig, scales, dt, w0=6.0, detrend=-1, output="pow", tpos=None,
-             ntime_out=None, chan_idx=None, accumulate=0, mode=0, nbmin=1024):
+             ntime_out=None, chan_idx=None, accumulate=0, mode=0, nbmin=1024, out=None):
     """`mode` as cwt.hip combines the kernel variants: bit 0 trial sums on pairs of segments (accumulate=2), bit 1 the direct
     kernels (1024- / 2048-point blocks, accumulate 0 / 1), bit 2 the channel-major input copy; `nbmin`: the shortest
-    block (build_groups)."""
+    block (build_groups); `out`: the array to store into / add to (a zeroed one by default)."""
     data = np.ascontiguousarray(data, dtype=np.float32)
     ld = data.shape[1]
     nchan = ld if chan_idx is None else len(chan_idx)
@@ -504,7 +504,10 @@ def cwt_exec(data, seg_start, trial_lo, trial_hi, nsig, scales, dt, w0=6.0, detr
     kind = OUT_KINDS[output]
     tp = None if tpos is None else np.ascontiguousarray(tpos, dtype=np.int32)
     nto = nsig if tpos is None else int(ntime_out)
-    out = np.zeros((1 if accumulate == 2 else len(ss), nto, len(scales), nchan), dtype=np.complex64 if kind == 2 else np.float32)
+    shape = (1 if accumulate == 2 else len(ss), nto, len(scales), nchan)
+    if out is None:
+        out = np.zeros(shape, dtype=np.complex64 if kind == 2 else np.float32)
+    assert out.shape == shape and out.flags.c_contiguous and out.dtype == (np.complex64 if kind == 2 else np.float32)
     rc = lib().emu_cwt(C.c_int(log2n), C.c_int(G), _p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int),
                        _p(ss, C.c_longlong), _p(tl, C.c_longlong), _p(th, C.c_longlong), C.c_int(len(ss)),
                        C.c_int(nsig), C.c_int(nchan), C.c_int(len(scales)), _p(tw, C.c_float),
@@ -513,6 +516,80 @@ def cwt_exec(data, seg_start, trial_lo, trial_hi, nsig, scales, dt, w0=6.0, detr
                        out.ctypes.data_as(C.c_void_p), C.c_int(accumulate), C.c_int(mode))
     assert rc == 0
     return out
+
+
+def cwt64_taps(nsig, scales, dt, w0=6.0, family=None, order=None, sl_cycles=None):
+    """The sampled kernels of spyhip_cwt_plan_create trimmed to the taps that can overlap a signal of nsig samples, and
+    each trimmed kernel's "same" offset: [(taps, centre)].  family None / "Paul" / "DOG" as O.cwt_kernel; `sl_cycles`:
+    MorletSL (O.cwt_sl)."""
+    from oracle import spy_oracle as O
+    out = []
+    for s in scales:
+        if sl_cycles is None:
+            h = O.cwt_kernel(s, dt, w0, family, order)
+        else:
+            M = 10 * s * sl_cycles / dt
+            t = np.arange((-M + 1) / 2.0, (M + 1) / 2.0) * dt
+            h = dt ** 0.5 / (4 * np.pi) * O.morlet_sl(t, s, sl_cycles)
+        h = np.asarray(h, dtype=np.complex128)
+        c = (h.size - 1) // 2
+        m0, m1 = max(0, c - (nsig - 1)), min(h.size, c + nsig)
+        out.append((h[m0:m1], c - m0))
+    return out
+
+
+def cwt64_tables(nsig, taps):
+    """NumPy mirror of spyhip_cwt_plan_set_precision: L = 2^m >= max(16, nsig + taps - 1), the length-L twiddles,
+    hspec64 = FFT_L(trimmed taps) / L, the centres."""
+    lmax = max(h.size for h, _ in taps)
+    L = 16
+    while L < nsig + lmax - 1:
+        L *= 2
+    hs = np.zeros((len(taps), L), dtype=np.complex128)
+    for s, (h, _) in enumerate(taps):
+        hs[s, :h.size] = h
+    hs = np.fft.fft(hs, axis=1) / L
+    hspec = np.ascontiguousarray(np.stack([hs.real, hs.imag], axis=-1))
+    centre = np.array([c for _, c in taps], dtype=np.int32)
+    return L, twiddles64(L), hspec, centre
+
+
+def cwt64_exec(data, seg_start, trial_lo, trial_hi, nsig, scales, dt, w0=6.0, family=None, order=None, sl_cycles=None,
+               detrend=-1, output="pow", tpos=None, ntime_out=None, chan_idx=None, accumulate=0, per_launch=None,
+               seg_chunk=None, out=None):
+    """Emulated spyhip_cwt_exec of a plan with spyhip_cwt_plan_set_precision(plan, 1) (cwt64_kernel.h): `per_launch`
+    (segment, channel) items per cwt64_kernel launch, `seg_chunk` segments per staging chunk (default: all at once).
+    `out`: the array to store into / add to (accumulate 1 / 2); a zeroed one otherwise."""
+    data = np.ascontiguousarray(data, dtype=np.float32)
+    ld = data.shape[1]
+    nchan = ld if chan_idx is None else len(chan_idx)
+    ci = None if chan_idx is None else np.ascontiguousarray(chan_idx, dtype=np.int32)
+    ss, tl, th = (np.ascontiguousarray(a, dtype=np.int64) for a in (seg_start, trial_lo, trial_hi))
+    nseg = len(ss)
+    L, tw, hspec, centre = cwt64_tables(nsig, cwt64_taps(nsig, scales, dt, w0, family, order, sl_cycles))
+    kind = OUT_KINDS[output]
+    tp = None if tpos is None else np.ascontiguousarray(tpos, dtype=np.int32)
+    nto = nsig if tpos is None else int(ntime_out)
+    shape = (1 if accumulate == 2 else nseg, nto, len(scales), nchan)
+    if out is None:
+        out = np.zeros(shape, dtype=np.complex64 if kind == 2 else np.float32)
+    assert out.shape == shape and out.flags.c_contiguous and out.dtype == (np.complex64 if kind == 2 else np.float32)
+    rc = lib().emu_cwt64(_p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int), _p(ss, C.c_longlong),
+                         _p(tl, C.c_longlong), _p(th, C.c_longlong), C.c_int(nseg), C.c_int(nsig), C.c_int(nchan),
+                         C.c_int(len(scales)), C.c_int(L), _p(tw, C.c_double), _p(hspec, C.c_double), _p(centre, C.c_int),
+                         C.c_int(detrend), C.c_int(kind), _p(tp, C.c_int), C.c_int(nto), out.ctypes.data_as(C.c_void_p),
+                         C.c_int(accumulate), C.c_longlong(per_launch or nseg * nchan), C.c_int(seg_chunk or nseg))
+    assert rc == 0, rc
+    return out
+
+
+def cwt_direct_fits(tpos, nsig, V, rowb, chanb):
+    """cwt_kernel.h: cwt_direct_fits - may the direct kernels write a plan with these slots, block groups and row bytes."""
+    tp = None if tpos is None else np.ascontiguousarray(tpos, dtype=np.int32)
+    v = np.ascontiguousarray(V, dtype=np.int32)
+    f = lib().emu_cwt_direct_fits
+    f.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_ulonglong, C.c_ulonglong]
+    return bool(f(_p(tp, C.c_int), nsig, _p(v, C.c_int), v.size, rowb, chanb))
 
 
 # ---------------------------------------------------------------- Wilson / Granger (mirror of the host loop in granger.hip)

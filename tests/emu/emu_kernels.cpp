@@ -27,6 +27,7 @@ thread_local BlockCtx* t_ctx = nullptr;
 #include "../../syncopy_amd/csrc/mtmfft_long.h"
 #include "../../syncopy_amd/csrc/mtmfft_declong.h"
 #include "../../syncopy_amd/csrc/cwt_kernel.h"
+#include "../../syncopy_amd/csrc/cwt64_kernel.h"
 #include "../../syncopy_amd/csrc/granger_kernels.h"
 #include "../../syncopy_amd/csrc/wilson_plus_kernel.h"
 #include "../../syncopy_amd/csrc/mtmfft_dec64_cfg.h"
@@ -832,6 +833,77 @@ int emu_cwt(int log2n, int G, const float* data, long long ld, const int* chan_i
     CWT2_CASE(10, 4) CWT2_CASE(11, 2) CWT2_CASE(12, 1) CWT2_CASE(13, 1)
 #undef CWT2_CASE
     return -1;
+}
+
+// CWT at reference precision (spyhip_cwt_exec with spyhip_cwt_plan_set_precision(plan, 1)): the trend kernels, cwt64_kernel
+// in launches of `per_launch` (segment, channel) items (cwt.hip: ~2 GiB of work arrays each), chunks of `seg_chunk`
+// segments (cwt.hip: ~4 GiB of staging each), and the transposition pass cwt.hip picks.  Tables (tw64, hspec64 with 1/L
+// folded in, centre) are built by the Python mirror of spyhip_cwt_plan_set_precision; the radix schedule here.
+int emu_cwt64(const float* data, long long ld, const int* chan_idx, const long long* seg_start, const long long* trial_lo,
+              const long long* trial_hi, int nseg, int nsig, int nchan, int nscales, int L, const double* tw64,
+              const double* hspec64, const int* centre, int detrend, int out_kind, const int* tpos, int ntime_out, void* out,
+              int accumulate, long long per_launch, int seg_chunk) {
+    spyfft::CwtArgs a{};
+    a.data = data; a.ld = ld; a.chan_idx = chan_idx; a.seg_start = seg_start; a.trial_lo = trial_lo; a.trial_hi = trial_hi;
+    a.nseg = nseg; a.nsig = nsig; a.nchan = nchan; a.nscales = nscales; a.nscales_total = nscales;
+    a.detrend = detrend; a.out_kind = out_kind; a.tpos = tpos; a.ntime_out = ntime_out; a.out = out; a.accumulate = accumulate;
+    std::vector<double> trend((size_t)nseg * nchan * 2, 0.0);
+    if (detrend >= 0) {
+        a.trend = trend.data();
+        if (detrend == 0) {
+            emu::launch(dim3((nchan + 63) / 64, nseg), dim3(64), 0, [&] { spyfft::cwt_mean_np_kernel(a, trend.data()); });
+        } else {
+            std::vector<double> part(trend.size() * spyfft::CWT_TREND_SPLITS, 0.0);
+            emu::launch(dim3((nchan + 63) / 64, spyfft::CWT_TREND_SPLITS, nseg), dim3(256), 0,
+                        [&] { spyfft::cwt_trend_partial_kernel(a, part.data()); });
+            emu::launch(dim3((unsigned)(((size_t)nseg * nchan + 255) / 256)), dim3(256), 0,
+                        [&] { spyfft::cwt_trend_final_kernel(a, part.data(), trend.data()); });
+        }
+    }
+    spyfft::Cwt64Args fa{};
+    fa.L = L;
+    if (!spywil::plus_plan(L, &fa.plan)) return -2;
+    fa.tw64 = reinterpret_cast<const double2*>(tw64);
+    fa.hspec64 = reinterpret_cast<const double2*>(hspec64);
+    fa.centre = centre;
+    const int outk = out_kind == SPYHIP_OUT_FOURIER ? 2 : (out_kind == SPYHIP_OUT_POW ? 0 : 1);
+    const size_t esz = outk == 2 ? 8 : 4;
+    if (seg_chunk < 1 || per_launch < 1) return -1;
+    const int chunk = std::min(seg_chunk, nseg);
+    std::vector<char> stage((size_t)chunk * nscales * nchan * nsig * esz);
+    std::vector<double2> work((size_t)per_launch * 3 * L);
+    fa.work = work.data();
+    for (int s0 = 0; s0 < nseg; s0 += chunk) {                // as the chunk loop of spyhip_cwt_exec
+        const int ns = std::min(chunk, nseg - s0);
+        spyfft::CwtArgs c = a;
+        c.seg0 = s0;
+        c.seg_start = a.seg_start + s0;
+        c.trial_lo = a.trial_lo + s0;
+        c.trial_hi = a.trial_hi + s0;
+        if (a.trend) c.trend = a.trend + (size_t)s0 * nchan * 2;
+        c.nseg = ns;
+        c.stage = stage.data();
+        fa.c = c;
+        const long long items = (long long)ns * nchan;
+        for (long long w0 = 0; w0 < items; w0 += per_launch) {
+            fa.wg0 = w0;
+            const unsigned g = (unsigned)std::min<long long>(per_launch, items - w0);
+            if (outk == 2) emu::launch(dim3(g), dim3(256), 0, [&] { spyfft::cwt64_kernel<2>(fa); });
+            else if (outk == 0) emu::launch(dim3(g), dim3(256), 0, [&] { spyfft::cwt64_kernel<0>(fa); });
+            else emu::launch(dim3(g), dim3(256), 0, [&] { spyfft::cwt64_kernel<1>(fa); });
+        }
+        const dim3 sg((nsig + 63) / 64, nscales, accumulate == 2 ? 1 : ns);
+        const bool wide = esz == 4 && (nsig & 3) == 0 && nsig >= 1024;
+        if (esz == 8) emu::launch(sg, dim3(256), 0, [&] { spyfft::cwt_scatter_kernel<float2>(c); });
+        else if (wide) emu::launch(dim3((nsig + 255) / 256, sg.y, sg.z), dim3(256), 0, [&] { spyfft::cwt_scatter_wide_kernel(c); });
+        else emu::launch(sg, dim3(256), 0, [&] { spyfft::cwt_scatter_kernel<float>(c); });
+    }
+    return 0;
+}
+
+// the plan-creation rule of cwt.hip for the direct kernels (cwt_kernel.h)
+int emu_cwt_direct_fits(const int* tpos, int nsig, const int* V, int ngroups, unsigned long long rowb, unsigned long long chanb) {
+    return spyfft::cwt_direct_fits(tpos, nsig, V, ngroups, rowb, chanb) ? 1 : 0;
 }
 
 // ---- Wilson / Granger kernels, one entry per kernel (the Python test re-creates the host loop of granger.hip)

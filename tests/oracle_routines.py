@@ -4,6 +4,8 @@ They reuse the product's front ends / engine (host logic) but replace every
 computeFunction by its NumPy restatement in oracle/spy_oracle.py, so that
 (a) the oracle can be pinned against the golden vectors through the same parameter
 mapping, and (b) GPU tests can compare product vs oracle on arbitrary inputs."""
+import contextlib
+
 import numpy as np
 
 from oracle import spy_oracle as O
@@ -100,3 +102,20 @@ ORACLE_FREQ = {"mtmfft": OracleMultiTaperFFT, "mtmconvol": OracleMultiTaperFFTCo
 ORACLE_CONN = {"csd": OracleCrossSpectra, "coh": OracleNormalizeCrossSpectra, "granger": OracleGrangerCausality,
                "dyadic": OracleSpectralDyadicProduct, "ppc": O.ppc,
                "ccov": OracleCrossCovariance, "ccov_norm": OracleNormalizeCrossCov}
+
+
+@contextlib.contextmanager
+def float64_fftconvolve():
+    """scipy.signal.fftconvolve fed float64 input while the block runs: the oracle's wavelet transforms (cwt_time, cwtSL)
+    in float64 arithmetic - the yardstick of precision="reference" (the reference's own fftconvolve transforms a float32
+    trial in single precision)."""
+    import scipy.signal as sps
+    keep = sps.fftconvolve
+
+    def conv64(in1, in2, mode="full", axes=None):
+        return keep(np.asarray(in1, dtype=np.float64), in2, mode=mode, axes=axes)
+    sps.fftconvolve = conv64
+    try:
+        yield
+    finally:
+        sps.fftconvolve = keep

@@ -8,6 +8,7 @@ import pytest
 import emu_driver as E
 from oracle import spy_oracle as O
 from parity import assert_parity, excess
+from cwt64_ref import assert_cwt64, cwt64_ref as _cwt64_ref
 
 
 def _fft_case(nsig, nfft, nchan, K, output, keeptapers, detrend, demean_taper=False, G=None, generic=False,
@@ -354,6 +355,191 @@ def test_cwt_trial_sums_on_pairs_of_trials(output, T):
     for mode, nbmin in ((1, 1024), (1 | 4, 1024), (1 | 4, 2048)):
         out = E.cwt_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, 6.0, 0, output, accumulate=2, mode=mode, nbmin=nbmin)
         assert_parity(out, ref.astype(out.dtype), what=f"pair sums, mode {mode}, blocks >= {nbmin}")
+
+
+# ---- K3 at reference precision (cwt64_kernel.h) and the direct kernels' slot bound ------------------------------------
+def _cwt64_data(seed, rows, ncol, offset=0.5):
+    rng = np.random.default_rng(seed)
+    t = np.arange(rows)[:, None] / 1000.0
+    return (rng.normal(size=(rows, ncol)) + offset + 3.0 * np.sin(2 * np.pi * 40.0 * t + np.arange(ncol))).astype("f4")
+
+
+@pytest.mark.parametrize("output", ["pow", "abs", "real", "imag", "fourier"])
+@pytest.mark.parametrize("detrend", [-1, 0, 1])
+def test_cwt64_kernel_outputs_and_detrending(output, detrend):
+    """Every output kind of cwt64_kernel and every detrending; the pre-selection starts inside the trial (seg_start !=
+    trial_lo) and the trial runs past it; 13 samples: a ragged transposition tile (nsig % 4 != 0)."""
+    nsig, nchan = 213, 3
+    data = _cwt64_data(5 + detrend, nsig + 60, nchan)
+    ss, lo, hi = np.array([17, 9]), np.array([5, 0]), np.array([5 + nsig + 40, nsig + 30])
+    scales = np.array([0.04, 0.012, 0.003])
+    got = E.cwt64_exec(data, ss, lo, hi, nsig, scales, 1e-3, detrend=detrend, output=output)
+    ref = _cwt64_ref(data, ss, lo, hi, nsig, scales, detrend, output)
+    if detrend == 1:
+        # the line fit is float64 here and float32 lstsq in the reference (VERDICT "What's missing", item 4)
+        assert_parity(got, ref, what=f"cwt64 {output} detrend 1")
+    else:
+        assert_cwt64(got, ref, output, f"cwt64 {output} detrend {detrend}")
+
+
+@pytest.mark.parametrize("family,order,sl_cycles", [("Paul", 4, None), ("DOG", 2, None), ("DOG", 6, None),
+                                                    (None, None, 3.0)])
+def test_cwt64_kernel_families(family, order, sl_cycles):
+    """Paul, DOG (m = 2: Ricker) and MorletSL taps through the same kernel; odd channel count, a chan_idx with a repeat."""
+    nsig = 301
+    data = _cwt64_data(11, nsig + 10, 6)
+    ci = np.array([4, 1, 4, 0, 5], dtype=np.int32)
+    ss, lo, hi = np.array([3]), np.array([0]), np.array([nsig + 10])
+    scales = np.array([0.02, 0.006]) if sl_cycles is None else np.array([0.004, 0.0015])
+    for output in ("fourier", "abs"):
+        got = E.cwt64_exec(data, ss, lo, hi, nsig, scales, 1e-3, family=family, order=order, sl_cycles=sl_cycles,
+                           detrend=0, output=output, chan_idx=ci)
+        ref = _cwt64_ref(data, ss, lo, hi, nsig, scales, 0, output, chan_idx=ci, family=family, order=order,
+                         sl_cycles=sl_cycles)
+        assert_cwt64(got, ref, output, f"cwt64 {family or 'MorletSL'} {output}")
+
+
+def test_cwt64_kernel_lengths():
+    """Transform lengths at their edges: the shortest (L = 16: 5 samples, 10 taps), kernels longer than the signal (trimmed
+    to the taps that overlap it), and nsig + taps - 1 landing exactly on a power of two and one beyond it."""
+    data = _cwt64_data(3, 1200, 2)
+    cases = [(5, np.array([0.001, 0.0008]), 16), (120, np.array([0.3, 0.05]), None)]
+    taps = E.cwt64_taps(1000, [0.02], 1e-3)[0][0].size
+    assert taps < 500
+    cases += [(512 - taps + 1, np.array([0.02, 0.005]), 512), (512 - taps + 2, np.array([0.02, 0.005]), 1024)]
+    for nsig, scales, L in cases:
+        Lp = E.cwt64_tables(nsig, E.cwt64_taps(nsig, scales, 1e-3))[0]
+        if L is not None:
+            assert Lp == L, (nsig, Lp, L)
+        else:
+            assert E.cwt64_taps(nsig, scales, 1e-3)[0][0].size < O.cwt_kernel(scales[0], 1e-3).size
+        ss = np.array([40, 0])
+        for output in ("fourier", "pow"):
+            got = E.cwt64_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, detrend=0, output=output)
+            ref = _cwt64_ref(data, ss, ss, ss + nsig, nsig, scales, 0, output)
+            assert_cwt64(got, ref, output, f"cwt64 nsig {nsig} L {Lp} {output}")
+
+
+@pytest.mark.parametrize("nseg,nchan,chunk", [(1, 7, 1), (7, 1, 5), (3, 3, 2)])
+def test_cwt64_kernel_launches_and_chunks(nseg, nchan, chunk):
+    """(segment, channel) items in launches of 3 (wg0 > 0, a ragged last launch) and segments in chunks (seg0 > 0, the
+    trend and segment tables offset per chunk), stored per segment and summed over the segments (accumulate 2)."""
+    nsig = 150
+    data = _cwt64_data(nseg * 10 + nchan, nseg * nsig + 50, nchan)
+    ss = np.arange(nseg) * nsig + 20
+    lo, hi = ss - 20, ss + nsig + 10
+    scales = np.array([0.01, 0.004])
+    for output in ("fourier", "real"):
+        ref = _cwt64_ref(data, ss, lo, hi, nsig, scales, 0, output)
+        got = E.cwt64_exec(data, ss, lo, hi, nsig, scales, 1e-3, detrend=0, output=output, per_launch=3, seg_chunk=chunk)
+        assert_cwt64(got, ref, output, f"cwt64 launches of 3, chunks of {chunk}, {output}")
+        tot = E.cwt64_exec(data, ss, lo, hi, nsig, scales, 1e-3, detrend=0, output=output, per_launch=3, seg_chunk=chunk,
+                           accumulate=2)
+        r = ref.astype(np.complex128)
+        assert_cwt64(tot, r.sum(axis=0, keepdims=True), output, f"cwt64 trial sum, {output}", nterms=nseg,
+                     scale=np.abs(r).sum(axis=0, keepdims=True))
+
+
+@pytest.mark.parametrize("output", ["pow", "fourier"])
+def test_cwt64_kernel_selection_and_accumulation(output):
+    """Post-selection (tpos, slots with gaps and unused samples): selected samples land in their slots, the others stay
+    untouched; accumulate 1 adds segment b to out[b]."""
+    nsig, nchan = 190, 4
+    data = _cwt64_data(7, 2 * nsig + 30, nchan)
+    ss = np.array([5, nsig + 20])
+    scales = np.array([0.015, 0.0035])
+    keep = np.r_[0:3, 10:150:7, 189]
+    tpos = np.full(nsig, -1, dtype=np.int32)
+    tpos[keep] = 2 * np.arange(keep.size) + 1                       # odd slots only
+    nto = 2 * keep.size + 1
+    ref = _cwt64_ref(data, ss, ss, ss + nsig, nsig, scales, 0, output)
+    got = E.cwt64_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, detrend=0, output=output, tpos=tpos, ntime_out=nto)
+    assert_cwt64(got[:, 1::2], ref[:, keep], output, f"cwt64 tpos {output}")
+    assert not got[:, 0::2].any()
+    rng = np.random.default_rng(1)
+    base = rng.normal(size=got.shape).astype(got.dtype)
+    if output == "fourier":
+        base = base + 1j * rng.normal(size=got.shape).astype(np.float32)
+    acc = E.cwt64_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, detrend=0, output=output, tpos=tpos, ntime_out=nto,
+                       accumulate=1, out=base.copy(), seg_chunk=1)
+    assert np.array_equal(acc[:, 0::2], base[:, 0::2])
+    b = base[:, 1::2].astype(np.complex128)
+    r = ref[:, keep].astype(np.complex128)
+    assert_cwt64(acc[:, 1::2] - b, r, output, f"cwt64 accumulate 1 {output}", scale=np.abs(r) + np.abs(b + r))
+
+
+def test_cwt64_kernel_wide_transposition():
+    """A real output with nsig % 4 == 0 and nsig >= 1024: cwt.hip transposes it with cwt_scatter_wide_kernel."""
+    nsig = 1024
+    data = _cwt64_data(2, nsig + 8, 3)
+    ss = np.array([4])
+    scales = np.array([0.006])
+    for output, acc in (("pow", 0), ("imag", 2)):
+        got = E.cwt64_exec(data, ss, ss - 4, ss + nsig + 4, nsig, scales, 1e-3, detrend=0, output=output, accumulate=acc)
+        ref = _cwt64_ref(data, ss, ss - 4, ss + nsig + 4, nsig, scales, 0, output)
+        assert_cwt64(got, ref, output, f"cwt64 wide transposition {output}")
+
+
+def test_cwt_direct_bound():
+    """cwt_direct_fits (cwt_kernel.h), the plan-creation rule for the direct kernels: slots increasing with the samples,
+    and every tile's slot span * rowb + channel bytes below 2^32 (32-bit store offsets from the tile's reference slot)."""
+    lim = 1 << 32
+    # contiguous slots: the span of a full block is V - 1; a ragged last block spans less
+    V, chanb = 1000, 256
+    rowb = (lim - chanb) // 999
+    assert E.cwt_direct_fits(None, 5000, [V], rowb, chanb)
+    assert not E.cwt_direct_fits(None, 5000, [V], rowb + 1, chanb)
+    assert E.cwt_direct_fits(None, 1500, [V], rowb, chanb)                # (the ragged last tile spans 499)
+    assert not E.cwt_direct_fits(None, 1500, [2000], rowb, chanb)         # one tile of 1500 samples spans 1499
+    assert E.cwt_direct_fits(None, 1500, [2000], (lim - chanb) // 1499, chanb)
+    # gapped slots tpos[n] = 10000 n: a 1004-sample tile spans 10 030 000 slots
+    tp = (10000 * np.arange(2048)).astype(np.int32)
+    assert E.cwt_direct_fits(tp, 2048, [1004], 256, 32)                   # 2.57e9 bytes
+    assert not E.cwt_direct_fits(tp, 2048, [1004], 512, 64)               # 5.14e9 bytes
+    assert not E.cwt_direct_fits(tp, 2048, [2000, 1004], 256, 32)         # a second group with longer tiles
+    span = 10000 * 1003
+    assert E.cwt_direct_fits(tp, 2048, [1004], (lim - 64) // span, 64)
+    assert not E.cwt_direct_fits(tp, 2048, [1004], (lim - 64) // span + 1, 64)
+    # unmapped samples: the tile's reference is the slot reached before it (0 before any) - the second tile [1004, 2008)
+    # spans 4e6 + 507 * 10000 slots from slot 0 though only its last 508 samples are mapped
+    tq = np.full(2048, -1, dtype=np.int32)
+    tq[1500:] = 10000 * np.arange(548) + 4000000
+    assert not E.cwt_direct_fits(tq, 2048, [1004], 512, 64)
+    assert E.cwt_direct_fits(tq, 2048, [1004], 256, 32)
+    tq[1500:] -= 4000000 - 5000
+    assert E.cwt_direct_fits(tq, 2048, [1004], 512, 64)
+    # slots not increasing
+    assert not E.cwt_direct_fits(np.r_[0, 2, 1].astype(np.int32), 3, [1004], 8, 8)
+    assert not E.cwt_direct_fits(np.r_[0, 1, 1].astype(np.int32), 3, [1004], 8, 8)
+    assert E.cwt_direct_fits(np.r_[0, -1, 1].astype(np.int32), 3, [1004], 8, 8)
+    # production shape (c4: 128 channels, 25 scales, complex): nowhere near
+    assert E.cwt_direct_fits(None, 16384, [1004, 1900], 25 * 128 * 8, 128 * 8)
+
+
+@pytest.mark.parametrize("output", ["pow", "fourier"])
+def test_cwt_direct_kernels_gapped_slots(output):
+    """cwt2d_kernel with slots far apart (tpos[n] = 7 n + 3, below the 32-bit bound): every sample in its slot, the slots
+    between untouched - zero after a store, the old values after accumulate 1."""
+    rng = np.random.default_rng(4)
+    nsig, nchan = 1400, 3
+    data = rng.normal(size=(2 * nsig + 30, nchan)).astype("f4") + 1.5
+    ss = np.array([10, nsig + 20])
+    lo, hi = ss.copy(), ss + nsig
+    scales = np.array([0.012, 0.004])
+    tpos = (7 * np.arange(nsig) + 3).astype(np.int32)
+    nto = 7 * nsig + 5
+    ref = np.stack([O.convert_output(O.cwt(O.detrend(np.array(data[a:a + nsig]), 0), 1000.0, scales).transpose(1, 0, 2), output)
+                    for a in ss])
+    out = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=nto, mode=2 | 4)
+    assert_parity(out[:, tpos], ref, what="direct cwt, gapped slots")
+    gap = np.ones(nto, dtype=bool)
+    gap[tpos] = False
+    assert not out[:, gap].any()
+    base = np.full(out.shape, 0.25, dtype=out.dtype)
+    acc = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=nto, mode=2 | 4,
+                     accumulate=1, out=base.copy())
+    assert np.array_equal(acc[:, gap], base[:, gap])
+    assert_parity(acc[:, tpos] - base[:, tpos], ref, what="direct cwt, gapped slots, accumulate 1")
 
 
 @pytest.mark.parametrize("n", [32, 37, 70])

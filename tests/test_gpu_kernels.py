@@ -845,9 +845,8 @@ def test_reference_precision_of_wavelets_and_superlets():
     SINGLE precision (error 1.5e-7 of the largest coefficient), so the yardstick is the oracle fed float64 trials: with a
     5 Hz line 60 dB above the noise the high-frequency scales - made of the noise alone - are exact to float32 rounding
     under precision="reference" and carry the line's transform error in the default kernels (and in the reference)."""
-    import scipy.signal as sps
     import syncopy_amd as spy
-    from oracle_routines import ORACLE_FREQ
+    from oracle_routines import ORACLE_FREQ, float64_fftconvolve
     from parity import excess
     rng = np.random.default_rng(21)
     nsamp, ntr, nchan = 3000, 2, 3
@@ -855,19 +854,12 @@ def test_reference_precision_of_wavelets_and_superlets():
     x = rng.normal(size=(nsamp * ntr, nchan)) + 1000.0 * np.sin(2 * np.pi * 5.0 * t)[:, None]
     trl = np.stack([np.arange(ntr) * nsamp, np.arange(1, ntr + 1) * nsamp, np.zeros(ntr)], axis=1)
     data = spy.AnalogData(x.astype(np.float32), samplerate=1000.0, trialdefinition=trl)
-    keep = sps.fftconvolve
-
-    def conv64(in1, in2, mode="full", axes=None):
-        return keep(np.asarray(in1, dtype=np.float64), in2, mode=mode, axes=axes)
     for kw in (dict(method="wavelet", foi=np.array([40.0, 90.0, 200.0]), output="fourier"),
                dict(method="wavelet", foi=np.array([60.0, 150.0]), output="pow", toi=np.arange(0.5, 2.5, 0.01)),
                dict(method="superlet", foi=np.array([50.0, 120.0, 250.0]), order_max=4, c_1=2, adaptive=True, output="abs")):
         ref = spy.freqanalysis(data, compute_method="sequential", routine_classes=ORACLE_FREQ, polyremoval=0, **kw)
-        sps.fftconvolve = conv64
-        try:
+        with float64_fftconvolve():
             ref64 = spy.freqanalysis(data, compute_method="sequential", routine_classes=ORACLE_FREQ, polyremoval=0, **kw)
-        finally:
-            sps.fftconvolve = keep
         exact = spy.freqanalysis(data, precision="reference", polyremoval=0, **kw)
         fast = spy.freqanalysis(data, polyremoval=0, **kw)
         b = np.asarray(ref64.data)
