@@ -434,6 +434,41 @@ int spyhip_trial_mean_c64(spyhip_ctx* ctx, const void* in_d, void* out_d, int64_
 int spyhip_axis_nanmean(spyhip_ctx* ctx, const void* x_d, int64_t outer, int64_t n, int64_t inner, int is_complex,
                         void* out_d);
 
+/* ---- spy.var / spy.std / spy.median / spy.itc (statistics/summary_stats.py:156-205, 321-486; statistics/compRoutines.py:
+ * 22-141).  All pointers are device pointers; the accumulators belong to the caller, who zeroes them before the first
+ * chunk, so trials can be streamed in chunks of any size with the same bits. */
+/* dim="trials", pass 1 (_trial_average, summary_stats.py:408-428): acc_d[i] += in_d[0, i] + ... + in_d[ntrials-1, i] in
+ * trial order, in float32; nfloat floats per trial (complex64: 2 per element, the components are summed apart) */
+int spyhip_trial_sum(spyhip_ctx* ctx, const void* in_d, float* acc_d, int64_t ntrials, int64_t nfloat);
+/* mean_d = acc_d / ntotal over n elements (float32: a division; complex64: times fl(1/ntotal), NumPy's Smith division by
+ * the real count); mean_d may be acc_d */
+int spyhip_trial_sum_finalize(spyhip_ctx* ctx, const float* acc_d, void* mean_d, int64_t ntotal, int64_t n, int is_complex);
+/* dim="trials", pass 2 (_trial_var, summary_stats.py:431-456): acc_d[i] (float32, n elements) += fl(|x - mean|)^2 over the
+ * chunk's trials in order; |.| of complex64 correctly rounded */
+int spyhip_trial_sqdev(spyhip_ctx* ctx, const void* in_d, const void* mean_d, float* acc_d, int64_t ntrials, int64_t n,
+                       int is_complex);
+/* out_d = acc_d / ntotal (complex64: times fl(1/ntotal), written as (v, 0)); take_sqrt: np.sqrt of it (spy.std,
+ * summary_stats.py:362) */
+int spyhip_trial_var_finalize(spyhip_ctx* ctx, const float* acc_d, void* out_d, int64_t ntotal, int64_t n, int is_complex,
+                              int take_sqrt);
+/* spy.itc pass (_trial_circ_average, summary_stats.py:459-486): acc_d[i] (complex64, n elements) += z / |z| over the
+ * chunk's trials in order; z = 0 or a non-finite z gives NaN */
+int spyhip_itc_accumulate(spyhip_ctx* ctx, const void* in_d, void* acc_d, int64_t ntrials, int64_t n);
+/* acc_d (outer, ntaper, inner) complex64 -> out_d (outer, inner) float32: / ntotal, mean over the tapers, |.| correctly
+ * rounded (summary_stats.py:364-373) */
+int spyhip_itc_finalize(spyhip_ctx* ctx, const void* acc_d, float* out_d, int64_t ntotal, int64_t outer, int64_t ntaper,
+                        int64_t inner);
+/* spy.var / spy.std (dim=<axis label>) for one trial (compRoutines.py:22-57: np.nanvar / np.nanstd(trial, axis,
+ * keepdims=True), ddof 0): x_d (outer, n, inner) float32 or complex64 -> out_d (outer, inner) of the same dtype (complex:
+ * imaginary part 0); NaN elements skipped, an all-NaN slice gives NaN */
+int spyhip_axis_nanvar(spyhip_ctx* ctx, const void* x_d, int64_t outer, int64_t n, int64_t inner, int is_complex,
+                       int take_sqrt, void* out_d);
+/* spy.median (dim=<axis label>) for one trial (np.nanmedian(trial, axis, keepdims=True)): x_d (outer, n, inner) float32
+ * or complex64 (ordered by real, then imaginary part) -> out_d (outer, inner); work_d holds outer*n*inner elements when
+ * inner > 1 (the slices are made contiguous there) and may be NULL otherwise; n < 2^31 */
+int spyhip_axis_nanmedian(spyhip_ctx* ctx, const void* x_d, int64_t outer, int64_t n, int64_t inner, int is_complex,
+                          void* work_d, void* out_d);
+
 #ifdef __cplusplus
 }
 #endif

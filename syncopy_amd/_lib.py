@@ -95,6 +95,14 @@ SIGNATURES = {
     "spyhip_trial_mean_f32": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64]),
     "spyhip_trial_mean_c64": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64]),
     "spyhip_axis_nanmean": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp]),
+    "spyhip_trial_sum": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64]),
+    "spyhip_trial_sum_finalize": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int]),
+    "spyhip_trial_sqdev": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int]),
+    "spyhip_trial_var_finalize": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "spyhip_itc_accumulate": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64]),
+    "spyhip_itc_finalize": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "spyhip_axis_nanvar": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, vp]),
+    "spyhip_axis_nanmedian": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, vp]),
 }
 
 

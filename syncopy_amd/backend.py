@@ -1128,3 +1128,110 @@ def trial_mean(x):
     else:
         check(ctx.lib.spyhip_trial_mean_f32(ctx.handle, _ptr(x), _ptr(out), T, n), "spyhip_trial_mean_f32")
     return out
+
+
+# ---- spy.var / spy.std / spy.median / spy.itc (csrc/stats.hip) ----------------------------------------------------
+def _stat_ctx(x):
+    ctx = context(x.device)
+    ctx.bind_stream()
+    return ctx
+
+
+def trial_sum(x, acc):
+    """acc += x[0] + x[1] + ... in trial order (float32 / complex64 chunk of trials; acc: same dtype, shape x.shape[1:])."""
+    assert x.is_cuda and x.dtype in (torch.float32, torch.complex64) and x.is_contiguous()
+    assert acc.dtype == x.dtype and acc.is_contiguous() and tuple(acc.shape) == tuple(x.shape[1:])
+    nfloat = acc.numel() * (2 if x.is_complex() else 1)
+    ctx = _stat_ctx(x)
+    check(ctx.lib.spyhip_trial_sum(ctx.handle, _ptr(x), _ptr(acc), x.shape[0], nfloat), "spyhip_trial_sum")
+    return acc
+
+
+def trial_sum_finalize(acc, ntotal):
+    """acc /= ntotal in place (complex64: times the float32 reciprocal, as trial_mean); returns acc, now the mean."""
+    assert acc.is_cuda and acc.dtype in (torch.float32, torch.complex64) and acc.is_contiguous()
+    ctx = _stat_ctx(acc)
+    check(ctx.lib.spyhip_trial_sum_finalize(ctx.handle, _ptr(acc), _ptr(acc), int(ntotal), acc.numel(),
+                                            int(acc.is_complex())), "spyhip_trial_sum_finalize")
+    return acc
+
+
+def trial_sqdev(x, mean, acc):
+    """acc (float32, shape x.shape[1:]) += fl(|x[t] - mean|)^2 over the chunk's trials in order."""
+    assert x.is_cuda and x.dtype in (torch.float32, torch.complex64) and x.is_contiguous()
+    assert mean.dtype == x.dtype and mean.is_contiguous() and tuple(mean.shape) == tuple(x.shape[1:])
+    assert acc.dtype == torch.float32 and acc.is_contiguous() and acc.numel() == mean.numel()
+    ctx = _stat_ctx(x)
+    check(ctx.lib.spyhip_trial_sqdev(ctx.handle, _ptr(x), _ptr(mean), _ptr(acc), x.shape[0], acc.numel(),
+                                     int(x.is_complex())), "spyhip_trial_sqdev")
+    return acc
+
+
+def trial_var_finalize(acc, ntotal, dtype, take_sqrt=False):
+    """acc / ntotal (then its sqrt) as a new tensor of `dtype` (complex64: imaginary part 0)."""
+    assert acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous()
+    assert dtype in (torch.float32, torch.complex64)
+    out = torch.empty(acc.shape, dtype=dtype, device=acc.device)
+    ctx = _stat_ctx(acc)
+    check(ctx.lib.spyhip_trial_var_finalize(ctx.handle, _ptr(acc), _ptr(out), int(ntotal), acc.numel(),
+                                            int(dtype == torch.complex64), int(bool(take_sqrt))),
+          "spyhip_trial_var_finalize")
+    return out
+
+
+def itc_accumulate(x, acc):
+    """acc (complex64, shape x.shape[1:]) += x[t] / |x[t]| over the chunk's trials in order."""
+    assert x.is_cuda and x.dtype == torch.complex64 and x.is_contiguous()
+    assert acc.dtype == torch.complex64 and acc.is_contiguous() and tuple(acc.shape) == tuple(x.shape[1:])
+    ctx = _stat_ctx(x)
+    check(ctx.lib.spyhip_itc_accumulate(ctx.handle, _ptr(x), _ptr(acc), x.shape[0], acc.numel()),
+          "spyhip_itc_accumulate")
+    return acc
+
+
+def itc_finalize(acc, ntotal, taper_axis):
+    """|mean over the taper axis of acc / ntotal| (float32, the taper axis kept with length 1)."""
+    assert acc.is_cuda and acc.dtype == torch.complex64 and acc.is_contiguous()
+    axis = taper_axis % acc.dim()
+    outer = int(np.prod(acc.shape[:axis], dtype=np.int64))
+    inner = int(np.prod(acc.shape[axis + 1:], dtype=np.int64))
+    shape = list(acc.shape)
+    shape[axis] = 1
+    out = torch.empty(shape, dtype=torch.float32, device=acc.device)
+    ctx = _stat_ctx(acc)
+    check(ctx.lib.spyhip_itc_finalize(ctx.handle, _ptr(acc), _ptr(out), int(ntotal), outer, int(acc.shape[axis]), inner),
+          "spyhip_itc_finalize")
+    return out
+
+
+def _axis_split(x, axis):
+    axis = axis % x.dim()
+    outer = int(np.prod(x.shape[:axis], dtype=np.int64))
+    inner = int(np.prod(x.shape[axis + 1:], dtype=np.int64))
+    shape = list(x.shape)
+    shape[axis] = 1
+    return outer, int(x.shape[axis]), inner, shape
+
+
+def axis_nanvar(x, axis, take_sqrt=False):
+    """np.nanvar (take_sqrt: np.nanstd)(x, axis, keepdims=True) of one trial array on the device, in x's dtype
+    (complex64: imaginary part 0; statistics/compRoutines.py:22-57)."""
+    assert x.is_cuda and x.dtype in (torch.float32, torch.complex64) and x.is_contiguous()
+    outer, n, inner, shape = _axis_split(x, axis)
+    out = torch.empty(shape, dtype=x.dtype, device=x.device)
+    ctx = _stat_ctx(x)
+    check(ctx.lib.spyhip_axis_nanvar(ctx.handle, _ptr(x), outer, n, inner, int(x.is_complex()), int(bool(take_sqrt)),
+                                     _ptr(out)), "spyhip_axis_nanvar")
+    return out
+
+
+def axis_nanmedian(x, axis):
+    """np.nanmedian(x, axis, keepdims=True) of one trial array on the device (complex64: lexicographic order)."""
+    assert x.is_cuda and x.dtype in (torch.float32, torch.complex64) and x.is_contiguous()
+    outer, n, inner, shape = _axis_split(x, axis)
+    out = torch.empty(shape, dtype=x.dtype, device=x.device)
+    work = torch.empty_like(x) if inner > 1 else None
+    ctx = _stat_ctx(x)
+    check(ctx.lib.spyhip_axis_nanmedian(ctx.handle, _ptr(x), outer, n, inner, int(x.is_complex()), _ptr(work),
+                                        _ptr(out)), "spyhip_axis_nanmedian")
+    return out
