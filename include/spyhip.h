@@ -469,6 +469,37 @@ int spyhip_axis_nanvar(spyhip_ctx* ctx, const void* x_d, int64_t outer, int64_t 
 int spyhip_axis_nanmedian(spyhip_ctx* ctx, const void* x_d, int64_t outer, int64_t n, int64_t inner, int is_complex,
                           void* work_d, void* out_d);
 
+/* ---- spy.preprocessing (preproc/preprocessing.py; preproc/compRoutines.py: detrending_cF, standardize_cF,
+ * but_filtering_cF, sinc_filtering_cF, rectify_cF; preproc/firws.py: apply_fir).  in_d / out_d: a batch of equal-length
+ * trials (ntrials, nsamp, nchan) float32 on the device, channel fastest; at most 2^31 - 1 elements per trial.  All
+ * buffers belong to the caller.  nan_d: one int32 per trial, zeroed by the caller; a call sets nan_d[t] = 1 when
+ * trial t of its input holds a NaN (the reference's has_nan) and never clears it.  rectify != 0 stores |.|
+ * (rectify_cF) instead of a pass of its own.  The filter designs (sos, zi, taps) are the caller's, in float64. */
+/* scipy.signal.detrend(trial, type="constant" | "linear", axis=0) for order 0 | 1.  Order 0 takes the float32 mean as
+ * NumPy does (rows added in time order, one division; pairwise when nchan == 1); order 1 fits the line in float64.
+ * out_d may be in_d. */
+int spyhip_detrend(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t ntrials, int64_t nsamp, int64_t nchan,
+                   int order, int rectify, int32_t* nan_d);
+/* (x - np.mean(x, 0)) / np.std(x, 0) per channel and trial in float32 with NumPy's summation order (standardize_cF
+ * after its optional detrend); out_d must not be in_d */
+int spyhip_standardize(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t ntrials, int64_t nsamp, int64_t nchan,
+                       int rectify, int32_t* nan_d);
+/* scipy.signal.sosfilt(sos, trial, axis=0): sos = nsec x 6 host doubles [b0 b1 b2 1 a1 a2], nsec <= 12; state and
+ * arithmetic in float64; out_d may be in_d */
+int spyhip_sosfilt(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t ntrials, int64_t nsamp, int64_t nchan,
+                   const double* sos, int nsec, int rectify, int32_t* nan_d);
+/* scipy.signal.sosfiltfilt(sos, trial, axis=0): zi = nsec x 2 host doubles (sosfilt_zi), edge = samples of odd
+ * extension at either end (SciPy's 3 * ntaps; nsamp > edge); work_d holds ntrials * (nsamp + 2 * edge) * nchan doubles
+ * (the forward pass in float64) */
+int spyhip_sosfiltfilt(spyhip_ctx* ctx, const float* in_d, float* out_d, double* work_d, int64_t ntrials, int64_t nsamp,
+                       int64_t nchan, const double* sos, const double* zi, int nsec, int edge, int rectify,
+                       int32_t* nan_d);
+/* scipy.signal.convolve(trial, taps[:, None], mode="same") as a direct float64 sum (apply_fir): taps_d = ntaps doubles
+ * ON THE DEVICE, any length (also longer than the trial); a NaN sample spoils the ntaps outputs around it in its own
+ * channel only; out_d must not be in_d */
+int spyhip_fir_same(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t ntrials, int64_t nsamp, int64_t nchan,
+                    const double* taps_d, int ntaps, int rectify, int32_t* nan_d);
+
 #ifdef __cplusplus
 }
 #endif

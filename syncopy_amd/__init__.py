@@ -18,7 +18,8 @@ from .shared.kwarg_decorators import StructDict, get_defaults  # noqa: F401
 # use; `syncopy_amd.abi` drives the same library with NumPy + ctypes only and never pulls torch in.
 _LAZY = {"freqanalysis": ".specest.freqanalysis", "connectivityanalysis": ".connectivity.connectivity_analysis",
          "mean": ".statistics.summary_stats", "var": ".statistics.summary_stats", "std": ".statistics.summary_stats",
-         "median": ".statistics.summary_stats", "itc": ".statistics.summary_stats"}
+         "median": ".statistics.summary_stats", "itc": ".statistics.summary_stats",
+         "preprocessing": ".preproc.preprocessing"}
 
 
 def release_device_buffers():

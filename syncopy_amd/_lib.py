@@ -103,6 +103,12 @@ SIGNATURES = {
     "spyhip_itc_finalize": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "spyhip_axis_nanvar": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, vp]),
     "spyhip_axis_nanmedian": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, vp]),
+    "spyhip_detrend": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, vp]),
+    "spyhip_standardize": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp]),
+    "spyhip_sosfilt": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, c_f64p, C.c_int, C.c_int, vp]),
+    "spyhip_sosfiltfilt": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, c_f64p, c_f64p, C.c_int, C.c_int,
+                                     C.c_int, vp]),
+    "spyhip_fir_same": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int, C.c_int, vp]),
 }
 
 

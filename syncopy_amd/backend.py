@@ -1235,3 +1235,67 @@ def axis_nanmedian(x, axis):
     check(ctx.lib.spyhip_axis_nanmedian(ctx.handle, _ptr(x), outer, n, inner, int(x.is_complex()), _ptr(work),
                                         _ptr(out)), "spyhip_axis_nanmedian")
     return out
+
+
+# ---- spy.preprocessing (csrc/preproc.hip) -------------------------------------------------------------------------
+def _pre_args(x, out, nan):
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == tuple(x.shape)
+    assert nan.dtype == torch.int32 and nan.is_contiguous() and nan.numel() == x.shape[0]
+    return _stat_ctx(x), (int(x.shape[0]), int(x.shape[1]), int(x.shape[2]))
+
+
+def _f64p(a):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def detrend(x, out, order, nan, rectify=False):
+    """out = scipy.signal.detrend(x, "constant" | "linear", axis=1) per trial of x (ntrials, nsamp, nchan) float32; out may
+    be x.  nan (int32 per trial, zeroed by the caller) is raised for trials that hold a NaN."""
+    ctx, shp = _pre_args(x, out, nan)
+    check(ctx.lib.spyhip_detrend(ctx.handle, _ptr(x), _ptr(out), *shp, int(order), int(rectify), _ptr(nan)),
+          "spyhip_detrend")
+    return out
+
+
+def standardize(x, out, nan, rectify=False):
+    """out = (x - mean) / std per channel and trial in float32 (NumPy's summation order); out is not x."""
+    ctx, shp = _pre_args(x, out, nan)
+    check(ctx.lib.spyhip_standardize(ctx.handle, _ptr(x), _ptr(out), *shp, int(rectify), _ptr(nan)),
+          "spyhip_standardize")
+    return out
+
+
+def sosfilt(x, out, sos, nan, rectify=False):
+    """out = scipy.signal.sosfilt(sos, x, axis=1) per trial (float64 recursion, float32 result); out may be x."""
+    ctx, shp = _pre_args(x, out, nan)
+    sos, sp = _f64p(sos)
+    check(ctx.lib.spyhip_sosfilt(ctx.handle, _ptr(x), _ptr(out), *shp, sp, int(sos.shape[0]), int(rectify), _ptr(nan)),
+          "spyhip_sosfilt")
+    return out
+
+
+def sosfiltfilt(x, out, sos, zi, edge, nan, rectify=False, work=None):
+    """out = scipy.signal.sosfiltfilt(sos, x, axis=1) per trial; zi = sosfilt_zi(sos), edge = SciPy's padding.  work:
+    float64 tensor of at least ntrials * (nsamp + 2 * edge) * nchan elements (allocated if None)."""
+    ctx, shp = _pre_args(x, out, nan)
+    sos, sp = _f64p(sos)
+    zi, zp = _f64p(zi)
+    need = shp[0] * (shp[1] + 2 * int(edge)) * shp[2]
+    if work is None:
+        work = torch.empty(need, dtype=torch.float64, device=x.device)
+    assert work.dtype == torch.float64 and work.is_contiguous() and work.numel() >= need
+    check(ctx.lib.spyhip_sosfiltfilt(ctx.handle, _ptr(x), _ptr(out), _ptr(work), *shp, sp, zp, int(sos.shape[0]),
+                                     int(edge), int(rectify), _ptr(nan)), "spyhip_sosfiltfilt")
+    return out
+
+
+def fir_same(x, out, taps, nan, rectify=False):
+    """out = scipy.signal.convolve(x, taps, "same") along time per trial and channel, a direct float64 sum; taps: float64
+    device tensor; out is not x."""
+    ctx, shp = _pre_args(x, out, nan)
+    assert taps.is_cuda and taps.dtype == torch.float64 and taps.is_contiguous() and taps.dim() == 1
+    check(ctx.lib.spyhip_fir_same(ctx.handle, _ptr(x), _ptr(out), *shp, _ptr(taps), int(taps.numel()), int(rectify),
+                                  _ptr(nan)), "spyhip_fir_same")
+    return out

@@ -173,6 +173,8 @@ class AnalogData(_Base):
         dev = torch.device("cuda" if device is None else device)
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
+        if self._data is None and self._pending is not None and self._device is not None and self._device.device == dev:
+            return self._device            # a result computed on the device whose host copy nobody has asked for yet
         span = self.shard_span()
         # the copy belongs to one host array in one orientation and one row span: a new array object, shape, dimord or
         # shard uploads again

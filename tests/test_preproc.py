@@ -1,0 +1,222 @@
+"""spy.preprocessing without a GPU: the filter design against recorded results of the reference's firws module, the
+front end driven by the NumPy / SciPy model (preproc_oracle.py), its argument checks, and a CPU emulation of the
+kernels of syncopy_amd/csrc/preproc_kernel.h against the model."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import scipy.signal as sps
+
+import syncopy_amd as spy
+import preproc_oracle as PO
+from parity import assert_parity
+from syncopy_amd.preproc import design
+from syncopy_amd.shared.errors import SPYTypeError, SPYValueError
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+G = np.load(os.path.join(HERE, "golden", "preproc.npz"))
+HOW = dict(compute_method="sequential", routine_classes=PO.PREPROC_OPS)
+
+
+def _data(lengths=(300, 200, 300), nchan=4, seed=0):
+    rng = np.random.default_rng(seed)
+    x = (rng.normal(size=(sum(lengths), nchan)) + 2.0).astype(np.float32)
+    e = np.concatenate([[0], np.cumsum(lengths)])
+    return spy.AnalogData(x, samplerate=1000.0, trialdefinition=np.stack([e[:-1], e[1:], np.zeros(len(lengths))], 1))
+
+
+# ---- design and oracle against the reference's recorded results ---------------------------------------------------
+def test_design_matches_recorded_reference():
+    for window in design.WINDOWS:
+        for order in (24, 31):
+            for ftype in design.FILTER_TYPES:
+                ref = G[f"wsinc_{window}_{order}_{ftype}"]
+                got = design.windowed_sinc(window, order, G[f"cut_{ftype}"], ftype)
+                assert got.shape == ref.shape == (order + order % 2 + 1,)
+                assert np.abs(got - ref).max() <= 1e-15
+    assert np.abs(design.minimum_phase(G["minphase_in"]) - G["minphase_out"]).max() <= 1e-14
+
+
+def test_oracle_fir_matches_recorded_reference():
+    for name in ("short", "long"):
+        got = PO.fir64(G["fir_trial"], G[f"fir_kernel_{name}"])
+        assert np.abs(got - G[f"fir_direct_{name}"]).max() <= 1e-14
+        assert_parity(got, G[f"fir_fft_{name}"], what=name)
+
+
+def test_butterworth_design_padding():
+    sos, zi, edge = design.butterworth(4, [20, 80], "bp", 1000.0)
+    assert sos.shape == (4, 6) and zi.shape == (4, 2) and edge == 27
+    sos, zi, edge = design.butterworth(3, 100, "lp", 1000.0)            # one zero-padded section
+    assert sos.shape == (2, 6) and edge == 12
+
+
+# ---- the front end with the model ---------------------------------------------------------------------------------
+def test_defaults_and_chain_order():
+    data = _data()
+    out = spy.preprocessing(data, freq=100, **HOW)
+    sos = sps.butter(4, 100, "lp", fs=1000.0, output="sos")
+    for g, x in zip(out.trials, data.trials):
+        assert np.array_equal(g, sps.sosfiltfilt(sos, x, axis=0).astype(np.float32))
+    assert out.data.dtype == np.float32 and list(out.channel) == list(data.channel) and out.samplerate == 1000.0
+    assert np.array_equal(out.trialdefinition, data.trialdefinition) and out.info["nan_trials"] == []
+
+    out = spy.preprocessing(data, filter_class="firws", freq=100, direction="onepass", **HOW)       # order 200
+    taps = design.windowed_sinc("hamming", 200, 0.1)
+    assert np.array_equal(out.trials[1], PO.fir(data.trials[1], taps))
+
+    out = spy.preprocessing(data, filter_class="firws", freq=[45, 55], filter_type="bs", order=31, polyremoval=1,
+                            zscore=True, rectify=True, direction="twopass", **HOW)
+    taps = design.windowed_sinc("hamming", 31, np.array([0.045, 0.055]), "bs")
+    x = data.trials[0]
+    x = PO.standardize(PO.detrend(x, 1))
+    x = PO.fir(PO.fir(PO.detrend(x, 1), taps), taps)
+    assert np.array_equal(out.trials[0], np.abs(x))
+    mp = spy.preprocessing(data, filter_class="firws", freq=100, order=30, direction="onepass-minphase", **HOW)
+    assert np.array_equal(mp.trials[2], PO.fir(data.trials[2], design.minimum_phase(design.windowed_sinc("hamming", 30, 0.1))))
+
+    z = spy.preprocessing(data, filter_class=None, zscore=True, rectify=True, **HOW)
+    assert np.array_equal(z.trials[2], np.abs(PO.standardize(data.trials[2]))) and "nan_trials" not in z.info
+    d = spy.preprocessing(data, filter_class=None, polyremoval=0, **HOW)
+    assert np.array_equal(d.trials[1], sps.detrend(data.trials[1], type="constant", axis=0))
+
+
+def test_select_cfg_and_nan_trials():
+    data = _data()
+    data.cfg = {"earlier": {"a": 1}}
+    data.data[300 + 57, 2] = np.nan
+    sel = {"trials": [2, 1], "channel": [3, 2], "latency": [0.02, 0.15]}
+    with pytest.warns(UserWarning, match="NaN"):
+        out = spy.preprocessing(data, filter_class="firws", freq=100, order=20, direction="onepass", select=sel, **HOW)
+    assert data.selection is None and out.info["nan_trials"] == [1] and list(out.channel) == list(data.channel[[3, 2]])
+    assert out.data.shape == (2 * 131, 2)
+    taps = design.windowed_sinc("hamming", 20, 0.1)
+    ref = PO.fir(data.trials[1][20:151][:, [3, 2]], taps)
+    assert np.array_equal(out.trials[1], ref, equal_nan=True) and np.isnan(ref[:, 1]).sum() == 21
+    assert out.cfg["earlier"] == {"a": 1} and out.cfg["preprocessing"]["order"] == 20
+    again = spy.preprocessing(out, filter_class=None, polyremoval=0, **HOW)
+    assert set(again.cfg) == {"earlier", "preprocessing"}
+    with pytest.warns(UserWarning, match="onepass"):
+        spy.preprocessing(data, freq=100, **HOW)
+    one = spy.preprocessing(data, filter_class=None, polyremoval=1, select={"trials": [1]}, **HOW)
+    assert np.isnan(one.data[:, 2]).all() and not np.isnan(one.data[:, [0, 1, 3]]).any()
+
+
+@pytest.mark.parametrize("kw,exc", [
+    (dict(filter_class="cheby", freq=10), SPYValueError), (dict(filter_type="xp", freq=10), SPYValueError),
+    (dict(filter_class="firws", window="kaiser", freq=10), SPYValueError), (dict(direction="both", freq=10), SPYValueError),
+    (dict(filter_class="firws", direction="up", freq=10), SPYValueError),
+    (dict(freq=501), SPYValueError), (dict(freq=-1), SPYValueError), (dict(freq=None), SPYTypeError),
+    (dict(filter_type="bp", freq=10), SPYValueError), (dict(filter_type="bs", freq=[1, 2, 3]), SPYValueError),
+    (dict(filter_type="bp", freq=[20, 20]), SPYValueError), (dict(filter_type="bp", freq=[20, 600]), SPYValueError),
+    (dict(freq=10, order=-2), SPYValueError), (dict(freq=10, order=2.5), SPYValueError),
+    (dict(freq=10, window="hann"), SPYValueError), (dict(freq=10, direction="onepass-minphase"), SPYValueError),
+    (dict(freq=10, polyremoval=2), SPYValueError), (dict(freq=10, polyremoval=0.5), SPYValueError),
+    (dict(freq=10, zscore=1), SPYValueError), (dict(freq=10, rectify="yes"), SPYValueError),
+    (dict(freq=10, rectify=True, hilbert="abs"), SPYValueError), (dict(freq=10, hilbert="phase"), SPYValueError),
+    (dict(filter_class=None), SPYValueError), (dict(freq=10, foo=1), SPYValueError),
+    (dict(freq=10, hilbert="abs"), NotImplementedError),
+])
+def test_argument_errors(kw, exc):
+    with pytest.raises(exc):
+        spy.preprocessing(_data(), **kw, **HOW)
+
+
+def test_input_errors_and_short_trials():
+    with pytest.raises(SPYTypeError):
+        spy.preprocessing(np.zeros((10, 2)), freq=10, **HOW)
+    with pytest.raises(SPYValueError):
+        spy.preprocessing(spy.AnalogData(), freq=10, **HOW)
+    with pytest.raises(ValueError, match="padlen"):
+        spy.preprocessing(_data(lengths=(300, 15)), freq=100, **HOW)
+    out = spy.preprocessing(_data(), filter_type="bp", freq=[80, 20], chan_per_worker=2, parallel=False, **HOW)
+    assert out.cfg["preprocessing"]["freq"] == [80, 20]
+    ref = sps.sosfiltfilt(sps.butter(4, [20, 80], "bp", fs=1000.0, output="sos"), _data().trials[0], axis=0)
+    assert np.array_equal(out.trials[0], ref.astype(np.float32))
+
+
+# ---- CPU emulation of preproc_kernel.h ----------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def emu():
+    src = os.path.join(HERE, "emu", "preproc_emu.cpp")
+    out = os.path.join(HERE, "emu", "_build", "libpreprocemu.so")
+    csrc = os.path.join(HERE, "..", "syncopy_amd", "csrc")
+    deps = [src, os.path.join(HERE, "emu", "hip_emu.h"), os.path.join(csrc, "preproc_kernel.h"), os.path.join(csrc, "np_sum.h")]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        clang = "/opt/rocm/lib/llvm/bin/clang++"
+        cxx = clang if os.path.exists(clang) else "g++"
+        subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-x", "c++", src, "-o", out])
+    lib = C.CDLL(out)
+    i, vp = C.c_int, C.c_void_p
+    lib.emu_detrend.argtypes = [vp, vp, i, i, i, i, i, vp]
+    lib.emu_standardize.argtypes = [vp, vp, i, i, i, i, vp]
+    lib.emu_sosfilt.argtypes = [vp, vp, i, i, i, vp, i, i, vp]
+    lib.emu_sosfiltfilt.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, vp]
+    lib.emu_fir_same.argtypes = [vp, vp, i, i, i, vp, i, i, vp]
+    return lib
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _batch(T, N, Cn, seed):
+    rng = np.random.default_rng(seed)
+    return (rng.normal(size=(T, N, Cn)) + rng.normal(size=(T, 1, Cn)) + 3.0).astype(np.float32)
+
+
+@pytest.mark.parametrize("shape", [(2, 300, 5), (3, 131, 1), (1, 9, 70)])
+def test_emu_detrend_and_standardize(emu, shape):
+    x = _batch(*shape, seed=1)
+    x[-1, 3, 0] = np.nan
+    flag = np.zeros(shape[0], np.int32)
+    out = np.empty_like(x)
+    emu.emu_detrend(_p(x), _p(out), *shape, 0, 0, _p(flag))
+    for t in range(shape[0]):
+        assert np.array_equal(out[t], PO.detrend(x[t], 0), equal_nan=True)           # NumPy's float32 order, bit for bit
+    assert list(flag) == [0] * (shape[0] - 1) + [1]
+    emu.emu_standardize(_p(x), _p(out), *shape, 1, _p(flag))
+    for t in range(shape[0]):
+        assert np.array_equal(out[t], np.abs(PO.standardize(x[t])), equal_nan=True)
+    emu.emu_detrend(_p(x), _p(out), *shape, 1, 0, _p(flag))
+    for t in range(shape[0]):
+        ref = PO.detrend(x[t], 1)
+        ok = ~np.isnan(ref)
+        assert np.array_equal(np.isnan(out[t]), ~ok)
+        assert_parity(out[t][ok], ref[ok], what="line fit")
+
+
+@pytest.mark.parametrize("ftype,freq,order", [("lp", 100, 4), ("bp", [20, 80], 4), ("bs", [45, 55], 3), ("hp", 30, 6)])
+def test_emu_sos(emu, ftype, freq, order):
+    shape = (2, 200, 3)
+    x = _batch(*shape, seed=2)
+    sos, zi, edge = design.butterworth(order, freq, ftype, 1000.0)
+    flag = np.zeros(2, np.int32)
+    out = np.empty_like(x)
+    emu.emu_sosfilt(_p(x), _p(out), *shape, _p(sos), sos.shape[0], 0, _p(flag))
+    for t in range(2):
+        assert_parity(out[t], PO.sosfilt(x[t], sos), what="sosfilt")
+    work = np.empty((2, 200 + 2 * edge, 3))
+    emu.emu_sosfiltfilt(_p(x), _p(out), _p(work), *shape, _p(sos), _p(zi), sos.shape[0], edge, 1, _p(flag))
+    for t in range(2):
+        assert_parity(out[t], np.abs(PO.sosfiltfilt(x[t], sos)), what="sosfiltfilt")
+    assert not flag.any()
+
+
+@pytest.mark.parametrize("N,Cn,ntaps", [(40, 3, 9), (33, 65, 17), (8, 2, 25), (23, 1, 8 + 1), (16, 4, 41)])
+def test_emu_fir(emu, N, Cn, ntaps):
+    x = _batch(2, N, Cn, seed=3)
+    x[1, N // 2, Cn - 1] = np.nan
+    taps = np.random.default_rng(4).normal(size=ntaps)
+    flag = np.zeros(2, np.int32)
+    out = np.empty_like(x)
+    emu.emu_fir_same(_p(x), _p(out), 2, N, Cn, _p(taps), ntaps, 0, _p(flag))
+    for t in range(2):
+        ref = PO.fir64(x[t], taps)
+        ok = ~np.isnan(ref)
+        assert np.array_equal(np.isnan(out[t]), ~ok)
+        assert_parity(out[t][ok], ref[ok], what="fir")
+    assert list(flag) == [0, 1]
