@@ -557,7 +557,7 @@ def test_blocked_inverse(n):
     assert info[0] == 2
 
 
-@pytest.mark.parametrize("n", [64, 37, 70])
+@pytest.mark.parametrize("n", [64, 37, 70, 97])
 def test_blocked_inverse_on_f64_matrix_cores(n):
     """zinv_mfma_kernel (32 x 32 blocks, R = D A_k* and the trailing update as v_mfma_f64_16x16x4_f64 tiles): ragged
     sizes (identity padding, partial tiles), asymmetric complex matrices (a row/column swap of a fragment layout would
@@ -574,7 +574,7 @@ def test_blocked_inverse_on_f64_matrix_cores(n):
     assert info[0] == 2
 
 
-@pytest.mark.parametrize("n", [128, 100, 192, 64])
+@pytest.mark.parametrize("n", [128, 100, 192, 64, 161])
 def test_blocked_inverse_with_64_row_blocks(n):
     """zinv64_mfma_kernel (64 x 64 diagonal blocks, the matrix walked in column quarters through a 64 x 64 R panel in
     LDS, the quarter of the block itself last): ragged sizes, asymmetric complex matrices, out of place, the tiny-pivot
@@ -662,6 +662,16 @@ def test_zgemm_fused_skew_and_error_check():
     ref = psi @ psi.conj().transpose(0, 2, 1) * (1 + herm + herm.transpose(0, 2, 1))        # Hermitian reference
     err = E.w_gemm_fused(psi, psi, opB=1, ref=ref)
     np.testing.assert_allclose(err, O.max_rel_err(ref, psi @ psi.conj().transpose(0, 2, 1)), rtol=1e-10)
+
+
+@pytest.mark.parametrize("n", [63, 65])
+def test_hermitian_zgemm_ragged_tiles(n):
+    """X X^H + I through the Hermitian instance (zgemm_mfma_kernel<3>) with one ragged tile (63) and with a ragged last
+    tile row whose mirror fills the column above it (65); nine matrices, so the batch is not a multiple of 8."""
+    rng = np.random.default_rng(n)
+    X = rng.normal(size=(9, n, n)) + 1j * rng.normal(size=(9, n, n))
+    np.testing.assert_allclose(E.w_gemm(X, X, opB=1, addI=1), X @ X.conj().transpose(0, 2, 1) + np.eye(n), rtol=1e-12,
+                               atol=1e-12)
 
 
 def test_wilson_building_blocks():
