@@ -499,6 +499,13 @@ int spyhip_sosfiltfilt(spyhip_ctx* ctx, const float* in_d, float* out_d, double*
  * channel only; out_d must not be in_d */
 int spyhip_fir_same(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t ntrials, int64_t nsamp, int64_t nchan,
                     const double* taps_d, int ntaps, int rectify, int32_t* nan_d);
+/* scipy.signal.resample_poly(trial, up, down, window=taps / up, axis=0) and trial[::down] (resample_cF, downsample_cF) as
+ * one up-FIR-down pass: out[m] = sum_i taps[m * down + (ntaps - 1) / 2 - i * up] * x[i] for m < nout, a float64 sum,
+ * in_d (ntrials, nsamp, nchan) -> out_d (ntrials, nout, nchan).  taps_d = ntaps doubles ON THE DEVICE, already
+ * multiplied by up, any length; up = 1 with the one tap 1.0 is the plain decimation, up = 1 with a filter keeps every
+ * down-th sample of spyhip_fir_same.  No NaN report; out_d must not be in_d */
+int spyhip_upfirdn(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t ntrials, int64_t nsamp, int64_t nchan,
+                   int64_t nout, const double* taps_d, int ntaps, int up, int down);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ from .shared.kwarg_decorators import StructDict, get_defaults  # noqa: F401
 _LAZY = {"freqanalysis": ".specest.freqanalysis", "connectivityanalysis": ".connectivity.connectivity_analysis",
          "mean": ".statistics.summary_stats", "var": ".statistics.summary_stats", "std": ".statistics.summary_stats",
          "median": ".statistics.summary_stats", "itc": ".statistics.summary_stats",
-         "preprocessing": ".preproc.preprocessing"}
+         "preprocessing": ".preproc.preprocessing", "resampledata": ".preproc.resampledata"}
 
 
 def release_device_buffers():

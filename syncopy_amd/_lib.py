@@ -109,6 +109,7 @@ SIGNATURES = {
     "spyhip_sosfiltfilt": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, c_f64p, c_f64p, C.c_int, C.c_int,
                                      C.c_int, vp]),
     "spyhip_fir_same": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int, C.c_int, vp]),
+    "spyhip_upfirdn": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int, C.c_int, C.c_int]),
 }
 
 

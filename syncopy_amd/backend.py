@@ -1299,3 +1299,18 @@ def fir_same(x, out, taps, nan, rectify=False):
     check(ctx.lib.spyhip_fir_same(ctx.handle, _ptr(x), _ptr(out), *shp, _ptr(taps), int(taps.numel()), int(rectify),
                                   _ptr(nan)), "spyhip_fir_same")
     return out
+
+
+def upfirdn(x, out, taps, up, down):
+    """out[m] = sum_i taps[m * down + (ntaps - 1) // 2 - i * up] * x[i] along time per trial and channel, a direct float64
+    sum: scipy.signal.resample_poly(x, up, down, window=taps / up) for out.shape[1] = ceil(nsamp * up / down), x[::down]
+    for up = 1 and taps = [1.0].  x (ntrials, nsamp, nchan), out (ntrials, nout, nchan) float32; taps: float64 device
+    tensor, already multiplied by up; out is not x."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
+    assert out.shape[0] == x.shape[0] and out.shape[2] == x.shape[2]
+    assert taps.is_cuda and taps.dtype == torch.float64 and taps.is_contiguous() and taps.dim() == 1
+    ctx = _stat_ctx(x)
+    check(ctx.lib.spyhip_upfirdn(ctx.handle, _ptr(x), _ptr(out), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]),
+                                 int(out.shape[1]), _ptr(taps), int(taps.numel()), int(up), int(down)), "spyhip_upfirdn")
+    return out

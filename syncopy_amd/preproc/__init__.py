@@ -1,2 +1,3 @@
-"""Time-domain preprocessing: `spy.preprocessing` (front end) and the host-side filter design."""
+"""Time-domain preprocessing: `spy.preprocessing` and `spy.resampledata` (front ends) and the host-side filter design."""
 from .preprocessing import preprocessing  # noqa: F401
+from .resampledata import resampledata  # noqa: F401

@@ -13,7 +13,8 @@ tests.  Trials of equal length are filtered together, at most CHUNK_BYTES of inp
 lives on the device is not uploaded again, and the result stays on the device for a following spy.freqanalysis (the
 host array is fetched when `.data` is first read).
 
-Not implemented: `hilbert=<output>` (raises NotImplementedError after validation) and spy.resampledata.
+Not implemented: `hilbert=<output>` (raises NotImplementedError after validation).  spy.resampledata lives in
+resampledata.py.
 """
 import numpy as np
 
