@@ -507,6 +507,16 @@ int spyhip_fir_same(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t nt
 int spyhip_upfirdn(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t ntrials, int64_t nsamp, int64_t nchan,
                    int64_t nout, const double* taps_d, int ntaps, int up, int down);
 
+/* ---- spy.timelockanalysis (statistics/timelockanalysis.py; statistics/compRoutines.py: cov_cF).  The channel
+ * covariance np.cov(trial, ddof=ddof, rowvar=False) of every trial of a batch of equal-length trials: x_d (ntrials, n,
+ * nchan) float32 on the device, channel fastest -> out_d (ntrials, nchan, nchan) float32.  Column means, centring,
+ * products and their sums in float64 (v_mfma_f64_16x16x4_f64), times 1.0 / (n - ddof), rounded to float32 once; the
+ * order of every sum is fixed, so two calls give the same bits.  A NaN in channel c of a trial makes row and column c
+ * of that trial's matrix NaN and nothing else.  ddof >= 0 and n - ddof > 0 (NumPy's ddof=None is 1); any nchan >= 1;
+ * out_d must not be x_d.  Uses the context's scratch buffer (ntrials * nchan doubles, at most 65535 trials' worth). */
+int spyhip_cov_f32(spyhip_ctx* ctx, const float* x_d, float* out_d, int64_t ntrials, int64_t n, int64_t nchan,
+                   int64_t ddof);
+
 #ifdef __cplusplus
 }
 #endif

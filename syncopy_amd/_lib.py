@@ -110,6 +110,7 @@ SIGNATURES = {
                                      C.c_int, vp]),
     "spyhip_fir_same": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int, C.c_int, vp]),
     "spyhip_upfirdn": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int, C.c_int, C.c_int]),
+    "spyhip_cov_f32": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
 }
 
 

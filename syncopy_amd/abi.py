@@ -211,6 +211,26 @@ class Device:
         acc.free()
         return res
 
+    # ---- spy.timelockanalysis
+    def cov(self, trials, ddof=None):
+        """np.cov(trial, ddof=ddof, rowvar=False) of every trial of `trials` (T, n, channels) float32: (T, channels,
+        channels) float32 (cov_cF; float64 arithmetic on the device, one rounding).  ddof=None is NumPy's default, 1."""
+        x = np.ascontiguousarray(trials, dtype=np.float32)
+        if x.ndim != 3:
+            raise ValueError("trials must be (T, n, channels)")
+        T, n, Cn = x.shape
+        xd = Buffer(self, x.shape, np.float32)
+        out = Buffer(self, (T, Cn, Cn), np.float32)
+        try:
+            check(self.lib.spyhip_upload(self.handle, xd.ptr, x.ctypes.data_as(C.c_void_p), x.nbytes), "spyhip_upload")
+            check(self.lib.spyhip_cov_f32(self.handle, xd.ptr, out.ptr, T, n, Cn, 1 if ddof is None else int(ddof)),
+                  "spyhip_cov_f32")
+            return out.numpy()
+        finally:
+            self.synchronize()
+            xd.free()
+            out.free()
+
     def close(self):
         if self.handle is not None:
             self.lib.spyhip_ctx_destroy(self.handle)

@@ -1314,3 +1314,19 @@ def upfirdn(x, out, taps, up, down):
     check(ctx.lib.spyhip_upfirdn(ctx.handle, _ptr(x), _ptr(out), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]),
                                  int(out.shape[1]), _ptr(taps), int(taps.numel()), int(up), int(down)), "spyhip_upfirdn")
     return out
+
+
+# ---- spy.timelockanalysis (csrc/cov.hip) --------------------------------------------------------------------------
+def cov(x, ddof=None, out=None):
+    """np.cov(x[t], ddof=ddof, rowvar=False) of every trial of x (ntrials, nsamp, nchan) float32 as float32 (ntrials,
+    nchan, nchan): means, centring and products in float64 on the matrix cores, one rounding at the end.  ddof=None is
+    NumPy's default, 1."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    T, n, nchan = (int(s) for s in x.shape)
+    if out is None:
+        out = torch.empty((T, nchan, nchan), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (T, nchan, nchan)
+    ctx = _stat_ctx(x)
+    check(ctx.lib.spyhip_cov_f32(ctx.handle, _ptr(x), _ptr(out), T, n, nchan, 1 if ddof is None else int(ddof)),
+          "spyhip_cov_f32")
+    return out

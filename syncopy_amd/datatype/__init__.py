@@ -6,6 +6,7 @@ Only the *layout contract* of the reference is kept (SURVEY.md section 8a, rows 
    [trialdefinition[t,0], trialdefinition[t,1]) with trigger offset trialdefinition[t,2];
  - SpectralData: dimord ["time","taper","freq","channel"] (continuous_data.py:550);
  - CrossSpectralData: dimord ["time","freq","channel_i","channel_j"] (continuous_data.py:721);
+ - TimeLockData: AnalogData's layout plus the datasets avg, var and cov of spy.timelockanalysis;
  - in-place selections {"trials","channel","latency"} (datatype/selector.py:126-454).
 HDF5 storage, Dask and the .spy container format are bypassed: the trial matrix is
 uploaded once to HBM (`AnalogData.device_data`) and stays there - the in-HBM trial queue.
@@ -246,6 +247,20 @@ class CrossSpectralData(_Base):
         self._dev_thunk = None
 
 
+class TimeLockData(_Base):
+    """Result of spy.timelockanalysis (datatype/continuous_data.py: TimeLockData): the selected, cut trials stacked along
+    time like AnalogData, plus the trial average `avg` and variance `var` (time x channel) and, if asked for, the
+    channel covariance `cov`; each of the three is None until it is computed."""
+    _defaultDimord = ["time", "channel"]
+
+    def __init__(self, data=None, samplerate=None, trialdefinition=None, channel=None, dimord=None):
+        super().__init__(data, samplerate, trialdefinition, dimord)
+        self.channel = None if channel is None else np.array(channel)
+        self.avg = None
+        self.var = None
+        self.cov = None
+
+
 class FauxTrial:
     """Shape/dtype stand-in of a trial for the dry run (datatype/base_data.py:1458)."""
 
@@ -273,6 +288,7 @@ class Selection:
         unknown = set(select) - {"trials", "channel", "latency"}
         if unknown:
             raise SPYValueError("keys 'trials', 'channel', 'latency'", varname="select", actual=str(sorted(unknown)))
+        self.select = dict(select)      # as given: what a front end that refines the selection starts from
         ntr = data.trialdefinition.shape[0]
         tr = select.get("trials")
         if tr is None or (isinstance(tr, str) and tr == "all"):
