@@ -162,6 +162,11 @@ class AnalogData(_Base):
             return 0, 0
         return int(min(a for a, _ in mine)), int(min(ntime, max(b for _, b in mine)))
 
+    def _device_copy_key(self, arr, dev, span):
+        """The device copy belongs to one host array in one orientation and one row span: a new array object, shape,
+        dimord or shard uploads again."""
+        return (id(arr), arr.shape, tuple(self.dimord), str(dev), span)
+
     def device_data(self, device=None, partial=False):
         """This rank's part of the (time x channel) float32 matrix in HBM (uploaded once, C-order, channel fastest): the
         rows `shard_span()`; `device_rows(data)` gives the trials in ITS row coordinates.
@@ -177,9 +182,7 @@ class AnalogData(_Base):
         if self._data is None and self._pending is not None and self._device is not None and self._device.device == dev:
             return self._device            # a result computed on the device whose host copy nobody has asked for yet
         span = self.shard_span()
-        # the copy belongs to one host array in one orientation and one row span: a new array object, shape, dimord or
-        # shard uploads again
-        key = (id(self._data), self._data.shape, tuple(self.dimord), str(dev), span)
+        key = self._device_copy_key(self._data, dev, span)
         if self._device is None or self._device_key != key:
             if getattr(self, "_upload", None) is not None:
                 self._upload.finish()      # a copy thread still writing into the tensor that is about to be dropped
@@ -193,6 +196,21 @@ class AnalogData(_Base):
             self._upload.finish()
             self._upload = None
         return self._device
+
+    def adopt_device_result(self, res):
+        """`res`, a (time x channel) float32 tensor a front end computed on the device, becomes this object's data:
+        device_data() hands it out with no round trip, and the host array is fetched when `.data` is first read."""
+        from .. import backend
+
+        def fetch():
+            arr = backend.to_host(res)
+            self._device_key = self._device_copy_key(arr, res.device, (0, arr.shape[0]))
+            return arr
+        self.set_pending(fetch, res.shape, np.float32)
+        self._device = res
+        self._device_key = None
+        self._row_origin = 0
+        self.staged_rows = (0, res.shape[0])
 
     def upload_in_flight(self):
         """backend.Upload of a device copy that is still being filled, or None."""
@@ -373,6 +391,11 @@ def device_rows(data):
 
 def selected_channels(data):
     return None if data.selection is None else list(data.selection.channel)
+
+
+def selected_channel_labels(data):
+    chans = selected_channels(data)
+    return np.array(data.channel) if chans is None else np.array(data.channel)[chans]
 
 
 def selected_trialdefinition(data):

@@ -9,17 +9,19 @@ The front end validates, designs the filter on the host in float64 (design.py) a
 reference's chain of steps: [detrend, z-score] if zscore, then [detrend, filter] (polyremoval is applied again by the
 filter routine, as there), |.| fused into the last step.  All arithmetic on samples runs in csrc/preproc.hip; there is
 no CPU path.  `compute_method="sequential"` with `routine_classes` swaps in a NumPy/SciPy model of the steps for the
-tests.  Trials of equal length are filtered together, at most CHUNK_BYTES of input at a time; an input that already
-lives on the device is not uploaded again, and the result stays on the device for a following spy.freqanalysis (the
-host array is fetched when `.data` is first read).
+tests.  Trials of equal length are filtered together, at most CHUNK_BYTES of input at a time, and reach the device by
+the routes of shared/trial_chunks.py; the result stays on the device for a following spy.freqanalysis
+(AnalogData.adopt_device_result).
 
 Not implemented: `hilbert=<output>` (raises NotImplementedError after validation).  spy.resampledata lives in
 resampledata.py.
 """
 import numpy as np
 
-from ..datatype import AnalogData, device_rows, selected_channels, selected_trialdefinition, trial_rows
+from ..datatype import AnalogData, selected_channel_labels, selected_trialdefinition, trial_rows
 from ..shared.errors import SPYInfo, SPYTypeError, SPYValueError, SPYWarning
+from ..shared.trial_chunks import (ResultRows, TrialSource, applied_selection, check_analog_input, check_scalar,
+                                   equal_length_chunks, reject_unknown_kwargs)
 from . import design
 
 __all__ = ["preprocessing"]
@@ -34,26 +36,9 @@ hilbert_outputs = {"abs", "complex", "real", "imag", "absreal", "absimag", "angl
 CHUNK_BYTES = 512 << 20
 
 
-def _is_int_like(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and float(v) == int(v)
-
-
-def _check_scalar(v, varname, lims, int_like=False):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise SPYTypeError(v, varname=varname, expected="scalar")
-    if not np.isfinite(v) and not (np.isinf(v) and np.isinf(lims[1]) and v > 0 and not int_like):
-        raise SPYValueError(f"value to be greater or equals {lims[0]} and less or equals {lims[1]}", varname=varname,
-                            actual=str(v))
-    if int_like and not _is_int_like(v):
-        raise SPYValueError("integer-like value", varname=varname, actual=str(v))
-    if v < lims[0] or v > lims[1]:
-        raise SPYValueError(f"value to be greater or equals {lims[0]} and less or equals {lims[1]}", varname=varname,
-                            actual=str(v))
-
-
 def _check_freq(freq, filter_type, nyquist):
     if filter_type in ("lp", "hp"):
-        _check_scalar(freq, "freq", [0, nyquist])
+        check_scalar(freq, "freq", [0, nyquist])
         return float(freq)
     try:
         arr = np.array(freq, dtype=float)
@@ -89,19 +74,12 @@ def preprocessing(data, filter_class="but", filter_type="lp", freq=None, order=N
 
     Returns float32 AnalogData with the input's dimord, channels and samplerate; `info["nan_trials"]` lists the trials
     whose input held a NaN when a filter or a detrending ran.  `chan_per_worker` / `parallel` are accepted and ignored."""
-    if not isinstance(data, AnalogData):
-        raise SPYTypeError(data, varname="data", expected="Syncopy AnalogData object")
-    if (data._data is None and data._pending is None) or data.trialdefinition is None:
-        raise SPYValueError("non-empty Syncopy data object", varname="data", actual="empty object")
-    if data.dimord.index("time") != 0:
-        raise SPYValueError("time x channel data", varname="data", actual=f"dimord {data.dimord}")
+    check_analog_input(data)
     defaults = dict(filter_class="but", filter_type="lp", freq=None, order=None, direction="twopass", window="hamming",
                     polyremoval=None, zscore=False, rectify=False, hilbert=False)
     given = dict(filter_class=filter_class, filter_type=filter_type, freq=freq, order=order, direction=direction,
                  window=window, polyremoval=polyremoval, zscore=zscore, rectify=rectify, hilbert=hilbert)
-    unknown = set(kwargs) - {"chan_per_worker", "parallel"}
-    if unknown:
-        raise SPYValueError(f"one of {sorted(defaults)}", varname="kwargs", actual=str(sorted(unknown)))
+    reject_unknown_kwargs(kwargs, defaults)
     new_cfg = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in given.items()}
     if select is not None:
         new_cfg["select"] = select
@@ -113,13 +91,13 @@ def preprocessing(data, filter_class="but", filter_type="lp", freq=None, order=N
             raise SPYValueError(f"one of {availableFilterTypes}", varname="filter_type", actual=filter_type)
         freq = _check_freq(freq, filter_type, data.samplerate / 2)
         if order is not None:
-            _check_scalar(order, "order", [0, np.inf], int_like=True)
+            check_scalar(order, "order", [0, np.inf], int_like=True)
             order = int(order)
     elif polyremoval is None and zscore is False:
         raise SPYValueError("a preprocessing method", varname="filter_class/polyremoval/zscore",
                             actual="neither filtering, detrending or zscore requested")
     if polyremoval is not None:
-        _check_scalar(polyremoval, "polyremoval", [0, 1], int_like=True)
+        check_scalar(polyremoval, "polyremoval", [0, 1], int_like=True)
         polyremoval = int(polyremoval)
     if not isinstance(zscore, bool):
         raise SPYValueError("either `True` or `False`", varname="zscore", actual=zscore)
@@ -131,10 +109,7 @@ def preprocessing(data, filter_class="but", filter_type="lp", freq=None, order=N
     if hilbert and hilbert not in hilbert_outputs:
         raise SPYValueError(f"one of {hilbert_outputs}", varname="hilbert", actual=hilbert)
 
-    had_selection = data.selection
-    if select is not None:
-        data.selectdata(select)
-    try:
+    with applied_selection(data, select):
         rows = trial_rows(data)
         if len(rows) < 1:
             raise SPYValueError("at least 1 trial", varname="data", actual="got 0 trials")
@@ -184,16 +159,14 @@ def preprocessing(data, filter_class="but", filter_type="lp", freq=None, order=N
             raise NotImplementedError(f"hilbert='{hilbert}' is not implemented: it needs an inverse transform of "
                                       "arbitrary trial length on the device")
 
-        if compute_method in (None, "hip"):
-            out_data, nan_flags = _device_run(data, rows, pre, main or [], rectify)
-        else:
-            out_data, nan_flags = _model_run(data, rows, pre, main or [], rectify, routine_classes)
-
         out = AnalogData(None, samplerate=data.samplerate, dimord=data.dimord)
-        out_data(out)
+        if compute_method in (None, "hip"):
+            res, nan_flags = _device_run(data, rows, pre, main or [], rectify)
+            out.adopt_device_result(res)            # stays on the device: no round trip before a spy.freqanalysis
+        else:
+            out.data, nan_flags = _model_run(data, rows, pre, main or [], rectify, routine_classes)
         out.trialdefinition = selected_trialdefinition(data)
-        chans = selected_channels(data)
-        out.channel = np.array(data.channel) if chans is None else np.array(data.channel)[chans]
+        out.channel = selected_channel_labels(data)
         if main is not None:
             nan_trials = [int(k) for k, f in enumerate(nan_flags) if f]
             if nan_trials:
@@ -205,21 +178,13 @@ def preprocessing(data, filter_class="but", filter_type="lp", freq=None, order=N
         out.cfg = dict(getattr(data, "cfg", {}) or {})
         out.cfg["preprocessing"] = new_cfg
         return out
-    finally:
-        data.selection = had_selection
-
-
-def _host_trials(data, rows):
-    chans = selected_channels(data)
-    full = chans is None or list(chans) == list(range(data.data.shape[1]))
-    return [data.data[a:b] if full else np.take(data.data[a:b], chans, axis=1) for a, b in rows]
 
 
 def _model_run(data, rows, pre, main, rectify, ops):
     """The chain through a table of host functions (the tests' NumPy/SciPy model): ops[step name](trial, *args) ->
     trial, ops["has_nan"](trial) -> bool, ops["rectify"](trial) -> trial."""
     outs, flags = [], []
-    for x in _host_trials(data, rows):
+    for x in TrialSource(data, rows).host_trials():
         x = np.array(x, dtype=np.float32)
         for step in pre:
             x = np.asarray(ops[step[0]](x, *step[1:]), dtype=np.float32)
@@ -229,11 +194,7 @@ def _model_run(data, rows, pre, main, rectify, ops):
         if rectify:
             x = np.asarray(ops["rectify"](x), dtype=np.float32)
         outs.append(x)
-    arr = np.concatenate(outs, axis=0)
-
-    def attach(out):
-        out.data = arr
-    return attach, flags
+    return np.concatenate(outs, axis=0), flags
 
 
 def _device_run(data, rows, pre, main, rectify):
@@ -244,97 +205,53 @@ def _device_run(data, rows, pre, main, rectify):
         raise SPYTypeError(data.data_dtype, varname="data", expected="float32 data")
     steps = list(pre) + list(main)
     first_main = len(pre)
-    chans = selected_channels(data)
-    resident = data._device is not None and getattr(data, "_upload", None) is None
-    src = data._device if resident else None
-    src_rows = device_rows(data) if resident else rows
-    nchan_in = int(data.data_shape[1])
-    full = chans is None or list(chans) == list(range(nchan_in))
-    nchan = nchan_in if full else len(chans)
-    dev = src.device if resident else torch.device("cuda", torch.cuda.current_device())
-    cidx = None if full else torch.as_tensor(list(chans), dtype=torch.int64, device=dev)
+    source = TrialSource(data, rows)
+    nchan, dev = source.nchan, source.dev
     lengths = [b - a for a, b in rows]
     starts = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
     res = torch.empty((int(starts[-1]), nchan), dtype=torch.float32, device=dev)
+    result = ResultRows(starts, res)
     flags = torch.zeros(len(rows), dtype=torch.int32, device=dev)
     taps_dev = {}
-    groups = {}
-    for k, n in enumerate(lengths):
-        groups.setdefault(n, []).append(k)
-    for n, members in groups.items():
-        if n < 1:
-            continue
-        per = max(1, CHUNK_BYTES // (n * nchan * 4))
-        for c0 in range(0, len(members), per):
-            ks = members[c0:c0 + per]
-            m = len(ks)
-            # input: a view of the resident matrix when the chunk's trials follow each other there, else gathered
-            if resident and full and all(src_rows[ks[i + 1]][0] == src_rows[ks[i]][1] for i in range(m - 1)):
-                x = src[src_rows[ks[0]][0]:src_rows[ks[-1]][1]].view(m, n, nchan)
-                owned = False
-            elif resident:
-                x = torch.stack([src[src_rows[k][0]:src_rows[k][1]] if full
-                                 else src[src_rows[k][0]:src_rows[k][1]].index_select(1, cidx) for k in ks])
-                owned = True
+    for n, ks in equal_length_chunks(lengths, nchan, CHUNK_BYTES):
+        m = len(ks)
+        x, owned = source.gather(ks, n)             # not owned: a view of the resident input, never written into
+        final = result.view(ks, n)                  # the last step writes straight into the result where it can
+        spare = None
+        nan_pre = torch.zeros(m, dtype=torch.int32, device=dev)
+        nan_main = torch.zeros(m, dtype=torch.int32, device=dev)
+        cur = x
+        for j, step in enumerate(steps):
+            last = j == len(steps) - 1
+            nan = nan_main if j >= first_main else nan_pre
+            in_place_ok = step[0] in ("detrend", "sosfilt", "sosfiltfilt") and (owned or cur is not x)
+            if last and final is not None:
+                dst = final
+            elif in_place_ok:
+                dst = cur
             else:
-                host = data.data
-                x = torch.empty((m, n, nchan), dtype=torch.float32, device=dev)
-                for i, k in enumerate(ks):
-                    a, b = rows[k]
-                    blk = host[a:b] if full else np.take(host[a:b], chans, axis=1)
-                    x[i].copy_(torch.from_numpy(np.ascontiguousarray(blk)))
-                owned = True
-            # output: straight into the result when the chunk's trials follow each other there
-            direct = all(ks[i + 1] == ks[i] + 1 for i in range(m - 1))
-            final = res[int(starts[ks[0]]):int(starts[ks[-1]] + n)].view(m, n, nchan) if direct else None
-            spare = None
-            nan_pre = torch.zeros(m, dtype=torch.int32, device=dev)
-            nan_main = torch.zeros(m, dtype=torch.int32, device=dev)
-            cur = x
-            for j, step in enumerate(steps):
-                last = j == len(steps) - 1
-                nan = nan_main if j >= first_main else nan_pre
-                in_place_ok = step[0] in ("detrend", "sosfilt", "sosfiltfilt") and (owned or cur is not x)
-                if last and final is not None:
-                    dst = final
-                elif in_place_ok:
-                    dst = cur
-                else:
-                    if spare is None or spare is cur:
-                        spare = torch.empty((m, n, nchan), dtype=torch.float32, device=dev)
-                    dst = spare
-                rect = rectify and last
-                if step[0] == "detrend":
-                    backend.detrend(cur, dst, step[1], nan, rect)
-                elif step[0] == "standardize":
-                    backend.standardize(cur, dst, nan, rect)
-                elif step[0] == "sosfilt":
-                    backend.sosfilt(cur, dst, step[1], nan, rect)
-                elif step[0] == "sosfiltfilt":
-                    backend.sosfiltfilt(cur, dst, step[1], step[2], step[3], nan, rect)
-                else:
-                    key = id(step[1])
-                    if key not in taps_dev:
-                        taps_dev[key] = torch.from_numpy(np.ascontiguousarray(step[1], dtype=np.float64)).to(dev)
-                    backend.fir_same(cur, dst, taps_dev[key], nan, rect)
-                if dst is not cur:
-                    spare = cur if (cur is not x or owned) else None
-                    cur = dst
-            if final is None:
-                for i, k in enumerate(ks):
-                    res[int(starts[k]):int(starts[k] + n)].copy_(cur[i])
-            flags[torch.as_tensor(ks, dtype=torch.int64, device=dev)] = nan_main
+                if spare is None or spare is cur:
+                    spare = torch.empty((m, n, nchan), dtype=torch.float32, device=dev)
+                dst = spare
+            rect = rectify and last
+            if step[0] == "detrend":
+                backend.detrend(cur, dst, step[1], nan, rect)
+            elif step[0] == "standardize":
+                backend.standardize(cur, dst, nan, rect)
+            elif step[0] == "sosfilt":
+                backend.sosfilt(cur, dst, step[1], nan, rect)
+            elif step[0] == "sosfiltfilt":
+                backend.sosfiltfilt(cur, dst, step[1], step[2], step[3], nan, rect)
+            else:
+                key = id(step[1])
+                if key not in taps_dev:
+                    taps_dev[key] = torch.as_tensor(np.ascontiguousarray(step[1], dtype=np.float64), device=dev)
+                backend.fir_same(cur, dst, taps_dev[key], nan, rect)
+            if dst is not cur:
+                spare = cur if (cur is not x or owned) else None
+                cur = dst
+        if final is None:
+            result.scatter(ks, n, cur)
+        flags[torch.as_tensor(ks, dtype=torch.int64, device=dev)] = nan_main
     flag_list = [bool(v) for v in flags.cpu().numpy()] if main else [False] * len(rows)
-    shape = (int(starts[-1]), nchan)
-
-    def attach(out):
-        def fetch():
-            arr = backend.to_host(res)
-            out._device_key = (id(arr), arr.shape, tuple(out.dimord), str(dev), (0, arr.shape[0]))
-            return arr
-        out.set_pending(fetch, shape, np.float32)
-        out._device = res                   # AnalogData.device_data() hands this out: no round trip before freqanalysis
-        out._device_key = None
-        out._row_origin = 0
-        out.staged_rows = (0, shape[0])
-    return attach, flag_list
+    return res, flag_list

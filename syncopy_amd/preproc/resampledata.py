@@ -10,8 +10,8 @@ scipy.signal.resample_poly(trial, up, down, window=taps) - one pass of the up-FI
 method="downsample": trial[::samplerate // resamplefs], after the two-pass windowed-sinc low-pass of spy.preprocessing
 when `lpfreq` is given; the second pass of that filter computes only the samples that are kept.  There is no CPU path;
 `compute_method="sequential"` with `routine_classes` swaps in a NumPy/SciPy model of the steps for the tests.  Trials of
-equal length go through the kernel together, at most CHUNK_BYTES of input at a time; an input that already lives on the
-device is not uploaded again, and the result stays on the device for a following spy.freqanalysis.
+equal length go through the kernel together, at most CHUNK_BYTES of input at a time, and reach the device by the routes
+of shared/trial_chunks.py; the result stays on the device for a following spy.freqanalysis.
 
 Deviations from the reference, on purpose:
   * lpfreq=0 with method="resample" raises SPYValueError (there a zero cut-off silently falls through to SciPy's Kaiser
@@ -28,10 +28,11 @@ from fractions import Fraction
 
 import numpy as np
 
-from ..datatype import AnalogData, device_rows, selected_channels, selected_trialdefinition, trial_rows
+from ..datatype import AnalogData, selected_channel_labels, selected_trialdefinition, trial_rows
 from ..shared.errors import SPYTypeError, SPYValueError, SPYWarning
+from ..shared.trial_chunks import (ResultRows, TrialSource, applied_selection, check_analog_input, check_scalar,
+                                   equal_length_chunks, reject_unknown_kwargs)
 from . import design
-from .preprocessing import _check_scalar, _host_trials
 
 __all__ = ["resampledata"]
 
@@ -57,27 +58,20 @@ def resampledata(data, resamplefs=1.0, method="resample", lpfreq=None, order=Non
     `chan_per_worker` / `parallel` are accepted and ignored."""
     if method not in availableMethods:
         raise SPYValueError("'downsample' or 'resample'", varname="method", actual=method)
-    if not isinstance(data, AnalogData):
-        raise SPYTypeError(data, varname="data", expected="Syncopy AnalogData object")
-    if (data._data is None and data._pending is None) or data.trialdefinition is None:
-        raise SPYValueError("non-empty Syncopy data object", varname="data", actual="empty object")
-    if data.dimord.index("time") != 0:
-        raise SPYValueError("time x channel data", varname="data", actual=f"dimord {data.dimord}")
-    unknown = set(kwargs) - {"chan_per_worker", "parallel"}
-    if unknown:
-        raise SPYValueError("one of ['lpfreq', 'method', 'order', 'resamplefs']", varname="kwargs", actual=str(sorted(unknown)))
+    check_analog_input(data)
     new_cfg = dict(resamplefs=resamplefs, method=method, lpfreq=lpfreq, order=order)
+    reject_unknown_kwargs(kwargs, new_cfg)
     if select is not None:
         new_cfg["select"] = select
     samplerate = float(data.samplerate)
-    _check_scalar(resamplefs, "resamplefs", [1, samplerate])
+    check_scalar(resamplefs, "resamplefs", [1, samplerate])
     if order is not None:
-        _check_scalar(order, "order", [0, np.inf], int_like=True)
+        check_scalar(order, "order", [0, np.inf], int_like=True)
         order = int(order)
         if order < 100:
             SPYWarning(f"You have chosen an anti-alias filter of very low `order={order}`, expect a slow roll-off!")
     if lpfreq is not None:
-        _check_scalar(lpfreq, "lpfreq", [0, resamplefs / 2])
+        check_scalar(lpfreq, "lpfreq", [0, resamplefs / 2])
     if method == "downsample":
         if samplerate % resamplefs != 0:
             raise SPYValueError("integer division of the original sampling rate for `method='downsample'`",
@@ -89,10 +83,7 @@ def resampledata(data, resamplefs=1.0, method="resample", lpfreq=None, order=Non
             SPYWarning("New sampling rate is integeger division of the original sampling rate, "
                        "consider using `method='downsample'`")
 
-    had_selection = data.selection
-    if select is not None:
-        data.selectdata(select)
-    try:
+    with applied_selection(data, select):
         rows = trial_rows(data)
         if len(rows) < 1:
             raise SPYValueError("at least 1 trial", varname="data", actual="got 0 trials")
@@ -116,41 +107,33 @@ def resampledata(data, resamplefs=1.0, method="resample", lpfreq=None, order=Non
             steps.append(("downsample", skip))
             out_lengths = (lengths + skip - 1) // skip
 
-        if compute_method in (None, "hip"):
-            attach = _device_run(data, rows, steps, out_lengths)
-        else:
-            attach = _model_run(data, rows, steps, out_lengths, routine_classes)
-
         out = AnalogData(None, samplerate=float(resamplefs), dimord=data.dimord)
-        attach(out)
+        if compute_method in (None, "hip"):
+            # the result stays on the device: no round trip before a spy.freqanalysis
+            out.adopt_device_result(_device_run(data, rows, steps, out_lengths))
+        else:
+            out.data = _model_run(data, rows, steps, out_lengths, routine_classes)
         edges = np.concatenate([[0], np.cumsum(out_lengths)])
         offsets = np.ceil(np.asarray(selected_trialdefinition(data))[:, 2] * resamplefs / samplerate)
         out.trialdefinition = np.stack([edges[:-1], edges[1:], offsets], axis=1)
-        chans = selected_channels(data)
-        out.channel = np.array(data.channel) if chans is None else np.array(data.channel)[chans]
+        out.channel = selected_channel_labels(data)
         out.cfg = dict(getattr(data, "cfg", {}) or {})
         out.cfg["resampledata"] = new_cfg
         return out
-    finally:
-        data.selection = had_selection
 
 
 def _model_run(data, rows, steps, out_lengths, ops):
     """The steps through a table of host functions (the tests' NumPy/SciPy model): ops["resample"](trial, taps_scaled, up,
     down), ops["downsample"](trial, skip), ops["fir"](trial, taps), each -> trial."""
     outs = []
-    for x, n in zip(_host_trials(data, rows), out_lengths):
+    for x, n in zip(TrialSource(data, rows).host_trials(), out_lengths):
         x = np.array(x, dtype=np.float32)
         for step in steps:
             x = np.asarray(ops[step[0]](x, *step[1:]), dtype=np.float32)
         if x.shape[0] != n:
             raise ValueError(f"the model returned {x.shape[0]} samples, expected {n}")
         outs.append(x)
-    arr = np.concatenate(outs, axis=0)
-
-    def attach(out):
-        out.data = arr
-    return attach
+    return np.concatenate(outs, axis=0)
 
 
 def _device_run(data, rows, steps, out_lengths):
@@ -159,71 +142,31 @@ def _device_run(data, rows, steps, out_lengths):
     backend.require_gpu()
     if data.data_dtype != np.float32:
         raise SPYTypeError(data.data_dtype, varname="data", expected="float32 data")
-    chans = selected_channels(data)
-    resident = data._device is not None and getattr(data, "_upload", None) is None
-    src = data._device if resident else None
-    src_rows = device_rows(data) if resident else rows
-    nchan_in = int(data.data_shape[1])
-    full = chans is None or list(chans) == list(range(nchan_in))
-    nchan = nchan_in if full else len(chans)
-    dev = src.device if resident else torch.device("cuda", torch.cuda.current_device())
-    cidx = None if full else torch.as_tensor(list(chans), dtype=torch.int64, device=dev)
+    source = TrialSource(data, rows)
+    nchan, dev = source.nchan, source.dev
     lengths = [b - a for a, b in rows]
     starts = np.concatenate([[0], np.cumsum(out_lengths)]).astype(np.int64)
     res = torch.empty((int(starts[-1]), nchan), dtype=torch.float32, device=dev)
+    result = ResultRows(starts, res)
     last = steps[-1]
     if last[0] == "resample":
         last_taps, up, down = last[1], last[2], last[3]
     else:                                           # the decimation, fused with the second filter pass if there is one
         last_taps, up, down = (steps[-2][1] if len(steps) > 1 else np.ones(1)), 1, last[1]
-    last_taps = torch.from_numpy(np.ascontiguousarray(last_taps, dtype=np.float64)).to(dev)
-    first_taps = torch.from_numpy(np.ascontiguousarray(steps[0][1], dtype=np.float64)).to(dev) if len(steps) > 1 else None
-    groups = {}
-    for k, n in enumerate(lengths):
-        groups.setdefault(n, []).append(k)
-    for n, members in groups.items():
-        if n < 1:
-            continue
-        nout = int(out_lengths[members[0]])
-        per = max(1, CHUNK_BYTES // (n * nchan * 4))
-        for c0 in range(0, len(members), per):
-            ks = members[c0:c0 + per]
-            m = len(ks)
-            # input: a view of the resident matrix when the chunk's trials follow each other there, else gathered
-            if resident and full and all(src_rows[ks[i + 1]][0] == src_rows[ks[i]][1] for i in range(m - 1)):
-                x = src[src_rows[ks[0]][0]:src_rows[ks[-1]][1]].view(m, n, nchan)
-            elif resident:
-                x = torch.stack([src[src_rows[k][0]:src_rows[k][1]] if full
-                                 else src[src_rows[k][0]:src_rows[k][1]].index_select(1, cidx) for k in ks])
-            else:
-                host = data.data
-                x = torch.empty((m, n, nchan), dtype=torch.float32, device=dev)
-                for i, k in enumerate(ks):
-                    a, b = rows[k]
-                    blk = host[a:b] if full else np.take(host[a:b], chans, axis=1)
-                    x[i].copy_(torch.from_numpy(np.ascontiguousarray(blk)))
-            if first_taps is not None:
-                # fir_same reports NaN trials; resampledata has no info["nan_trials"], so the flags are not read
-                nan = torch.zeros(m, dtype=torch.int32, device=dev)
-                x = backend.fir_same(x, torch.empty((m, n, nchan), dtype=torch.float32, device=dev), first_taps, nan)
-            # output: straight into the result when the chunk's trials follow each other there
-            direct = all(ks[i + 1] == ks[i] + 1 for i in range(m - 1))
-            if direct:
-                backend.upfirdn(x, res[int(starts[ks[0]]):int(starts[ks[-1]] + nout)].view(m, nout, nchan), last_taps, up, down)
-            else:
-                y = backend.upfirdn(x, torch.empty((m, nout, nchan), dtype=torch.float32, device=dev), last_taps, up, down)
-                for i, k in enumerate(ks):
-                    res[int(starts[k]):int(starts[k] + nout)].copy_(y[i])
-    shape = (int(starts[-1]), nchan)
-
-    def attach(out):
-        def fetch():
-            arr = backend.to_host(res)
-            out._device_key = (id(arr), arr.shape, tuple(out.dimord), str(dev), (0, arr.shape[0]))
-            return arr
-        out.set_pending(fetch, shape, np.float32)
-        out._device = res                   # AnalogData.device_data() hands this out: no round trip before freqanalysis
-        out._device_key = None
-        out._row_origin = 0
-        out.staged_rows = (0, shape[0])
-    return attach
+    last_taps = torch.as_tensor(np.ascontiguousarray(last_taps, dtype=np.float64), device=dev)
+    first_taps = torch.as_tensor(np.ascontiguousarray(steps[0][1], dtype=np.float64), device=dev) if len(steps) > 1 else None
+    for n, ks in equal_length_chunks(lengths, nchan, CHUNK_BYTES):
+        m, nout = len(ks), int(out_lengths[ks[0]])
+        x, _ = source.gather(ks, n)
+        if first_taps is not None:
+            # fir_same reports NaN trials; resampledata has no info["nan_trials"], so the flags are not read
+            nan = torch.zeros(m, dtype=torch.int32, device=dev)
+            x = backend.fir_same(x, torch.empty((m, n, nchan), dtype=torch.float32, device=dev), first_taps, nan)
+        # output: straight into the result when the chunk's trials follow each other there
+        direct = result.view(ks, nout)
+        if direct is not None:
+            backend.upfirdn(x, direct, last_taps, up, down)
+        else:
+            y = backend.upfirdn(x, torch.empty((m, nout, nchan), dtype=torch.float32, device=dev), last_taps, up, down)
+            result.scatter(ks, nout, y)
+    return res

@@ -175,11 +175,7 @@ def _statistic(spy_data, dim, op, keeptrials, select, compute_method, routine_cl
         seldef = (spy_data.trialdefinition if spy_data.selection is None else spy_data.selection.trialdefinition)
         ops = _device_ops() if compute_method in (None, "hip") else routine_classes
         if dim == "trials":
-            shape0 = trials[0][0].shape
-            for x, _ in trials:
-                if x.shape != shape0:
-                    raise SPYValueError("all trials to have the same shape", varname="in_data",
-                                        actual=f"found trials of different shape: {shape0} and {x.shape}")
+            _check_equal_trials(trials)
             if op == "median":
                 raise NotImplementedError("Trial median not supported at the moment")     # summary_stats.py:380-382
             res = ops["trial_" + op]([x for x, _ in trials])
@@ -216,23 +212,17 @@ def _device_ops():
     def to_dev(x):
         return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
-    def trial_mean(trials):
-        stacked = torch.stack([to_dev(x) for x in trials])
-        if stacked.dtype not in (torch.float32, torch.complex64):
-            raise SPYTypeError(stacked.dtype, varname="data", expected="float32 or complex64 data")
-        return backend.to_host(backend.trial_mean(stacked.contiguous()))
-
-    def axis_mean(x, axis):
-        d = to_dev(x)
-        if d.dtype not in (torch.float32, torch.complex64):
-            raise SPYTypeError(d.dtype, varname="data", expected="float32 or complex64 data")
-        return backend.to_host(backend.axis_nanmean(d, axis))
-
     def checked(x):
         d = to_dev(x)
         if d.dtype not in (torch.float32, torch.complex64):
             raise SPYTypeError(d.dtype, varname="data", expected="float32 or complex64 data")
         return d
+
+    def trial_mean(trials):
+        return backend.to_host(backend.trial_mean(torch.stack([checked(x) for x in trials]).contiguous()))
+
+    def axis_mean(x, axis):
+        return backend.to_host(backend.axis_nanmean(checked(x), axis))
 
     def upload(trials):
         first = checked(trials[0])

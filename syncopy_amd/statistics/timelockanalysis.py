@@ -9,9 +9,9 @@ timelockanalysis.py with cov_cF / Covariance of statistics/compRoutines.py), on 
 `tld.data`.  `avg` and `var` go through the kernels of spy.mean / spy.var (sequential float32 sum over the trials, two-pass
 variance), `cov` through the fp64 matrix-core kernel of csrc/cov.hip: np.cov per trial in float64, rounded to float32
 once, then - unless keeptrials - the engine's trial average, a sequential float32 sum and one division.  The trials pass
-through the device in chunks of at most CHUNK_BYTES, an input that already lives there is not uploaded again, and there is
-no CPU path; `compute_method="sequential"` with `routine_classes` swaps in a table of NumPy functions (trial_mean,
-trial_var, cov) for the tests.
+through the device in chunks of at most CHUNK_BYTES, by the routes of shared/trial_chunks.py, and there is no CPU path;
+`compute_method="sequential"` with `routine_classes` swaps in a table of NumPy functions (trial_mean, trial_var, cov) for
+the tests.
 
 Deviations from the reference, on purpose:
   * n - ddof <= 0 raises SPYValueError (there NumPy warns and the result is inf / NaN);
@@ -22,8 +22,10 @@ Deviations from the reference, on purpose:
 """
 import numpy as np
 
-from ..datatype import (AnalogData, TimeLockData, device_rows, selected_channels, selected_trialdefinition, trial_rows)
+from ..datatype import TimeLockData, selected_channel_labels, selected_channels, selected_trialdefinition, trial_rows
 from ..shared.errors import SPYTypeError, SPYValueError
+from ..shared.trial_chunks import (TrialSource, applied_selection, check_analog_input, equal_length_chunks,
+                                   reject_unknown_kwargs)
 
 __all__ = ["timelockanalysis"]
 
@@ -45,12 +47,7 @@ def timelockanalysis(data, latency="maxperiod", covariance=False, ddof=None, tri
     Returns TimeLockData: `data` holds the selected trials cut to the window and stacked along time, `avg` and `var` are
     (nSamples, nChannels), `cov` is None, (nChannels, nChannels) or (nTrials, nChannels, nChannels), squeezed.  All cut
     trials need the same length.  `chan_per_worker` / `parallel` are accepted and ignored."""
-    if not isinstance(data, AnalogData):
-        raise SPYTypeError(data, varname="data", expected="Syncopy AnalogData object")
-    if (data._data is None and data._pending is None) or data.trialdefinition is None:
-        raise SPYValueError("non-empty Syncopy data object", varname="data", actual="empty object")
-    if data.dimord.index("time") != 0:
-        raise SPYValueError("time x channel data", varname="data", actual=f"dimord {data.dimord}")
+    check_analog_input(data)
     if data.data_dtype != np.float32:
         raise SPYTypeError(data.data_dtype, varname="data", expected="float32 data")
     if ddof is not None and (not isinstance(ddof, int) or isinstance(ddof, bool) or ddof < 0):
@@ -59,19 +56,13 @@ def timelockanalysis(data, latency="maxperiod", covariance=False, ddof=None, tri
         raise SPYTypeError(covariance, varname="covariance", expected="bool")
     if not isinstance(keeptrials, bool):
         raise SPYTypeError(keeptrials, varname="keeptrials", expected="bool")
-    unknown = set(kwargs) - {"chan_per_worker", "parallel"}
-    if unknown:
-        raise SPYValueError("one of ['covariance', 'ddof', 'keeptrials', 'latency', 'trials']", varname="kwargs",
-                            actual=str(sorted(unknown)))
     new_cfg = dict(latency=latency, covariance=covariance, ddof=ddof, trials=trials, keeptrials=keeptrials)
+    reject_unknown_kwargs(kwargs, new_cfg)
     if select is not None:
         new_cfg["select"] = select
     all_trials = isinstance(trials, str) and trials == "all"
 
-    had_selection = data.selection
-    try:
-        if select is not None:
-            data.selectdata(select)
+    with applied_selection(data, select):
         sel = {} if data.selection is None else dict(data.selection.select)
         if not all_trials:
             if sel.get("trials") is not None:
@@ -100,7 +91,7 @@ def timelockanalysis(data, latency="maxperiod", covariance=False, ddof=None, tri
 
         tld = TimeLockData(None, samplerate=data.samplerate, dimord=data.dimord)
         tld.trialdefinition = selected_trialdefinition(data)
-        tld.channel = np.array(data.channel) if chans is None else np.array(data.channel)[chans]
+        tld.channel = selected_channel_labels(data)
         tld.cfg = dict(getattr(data, "cfg", {}) or {})
         tld.cfg["timelockanalysis"] = new_cfg
         if compute_method in (None, "hip"):
@@ -108,23 +99,12 @@ def timelockanalysis(data, latency="maxperiod", covariance=False, ddof=None, tri
         else:
             _model_run(data, tld, rows, covariance, ddof, keeptrials, routine_classes)
         return tld
-    finally:
-        data.selection = had_selection
-
-
-def _host_stack(data, rows, chans):
-    """the selected rows and channels of the host matrix, stacked in trial order (a view when they are one block)"""
-    host = data.data
-    full = chans is None or list(chans) == list(range(host.shape[1]))
-    if full and all(rows[i + 1][0] == rows[i][1] for i in range(len(rows) - 1)):
-        return host[rows[0][0]:rows[-1][1]]
-    return np.concatenate([host[a:b] if full else np.take(host[a:b], chans, axis=1) for a, b in rows], axis=0)
 
 
 def _model_run(data, tld, rows, covariance, ddof, keeptrials, ops):
     """Through a table of host functions (the tests' NumPy model): ops["trial_mean"](trials), ops["trial_var"](trials),
     ops["cov"](trial, ddof) -> float32 (nchan, nchan)."""
-    stacked = np.asarray(_host_stack(data, rows, selected_channels(data)), dtype=np.float32)
+    stacked = np.asarray(TrialSource(data, rows).host_stack(), dtype=np.float32)
     n = rows[0][1] - rows[0][0]
     trials = [stacked[k * n:(k + 1) * n] for k in range(len(rows))]
     tld.data = stacked
@@ -140,34 +120,10 @@ def _device_run(data, tld, rows, n, covariance, ddof, keeptrials):
     import torch
     from .. import backend
     backend.require_gpu()
-    chans = selected_channels(data)
-    resident = data._device is not None and getattr(data, "_upload", None) is None
-    src = data._device if resident else None
-    src_rows = device_rows(data) if resident else rows
-    nchan_in = int(data.data_shape[1])
-    full = chans is None or list(chans) == list(range(nchan_in))
-    nchan = nchan_in if full else len(chans)
-    dev = src.device if resident else torch.device("cuda", torch.cuda.current_device())
-    cidx = None if full else torch.as_tensor(list(chans), dtype=torch.int64, device=dev)
+    source = TrialSource(data, rows)
+    nchan, dev = source.nchan, source.dev
     T = len(rows)
-    per = max(1, CHUNK_BYTES // (n * nchan * 4))
-    spans = [(a, min(T, a + per)) for a in range(0, T, per)]
-
-    def chunk(k0, k1):
-        """trials k0 ... k1 - 1 as (m, n, nchan) on the device: a view of the resident matrix when they follow each other
-        there, else gathered or uploaded"""
-        if resident and full and all(src_rows[k + 1][0] == src_rows[k][1] for k in range(k0, k1 - 1)):
-            return src[src_rows[k0][0]:src_rows[k1 - 1][1]].view(k1 - k0, n, nchan)
-        if resident:
-            return torch.stack([src[src_rows[k][0]:src_rows[k][1]] if full
-                                else src[src_rows[k][0]:src_rows[k][1]].index_select(1, cidx) for k in range(k0, k1)])
-        host = data.data
-        x = torch.empty((k1 - k0, n, nchan), dtype=torch.float32, device=dev)
-        for i, k in enumerate(range(k0, k1)):
-            a, b = rows[k]
-            blk = host[a:b] if full else np.take(host[a:b], chans, axis=1)
-            x[i].copy_(torch.from_numpy(np.ascontiguousarray(blk)))
-        return x
+    chunks = [ks for _, ks in equal_length_chunks([n] * T, nchan, CHUNK_BYTES)]     # runs of consecutive trials
 
     # pass 1: the trial sum, and the covariance of every trial while it is on the device
     acc = torch.zeros((n, nchan), dtype=torch.float32, device=dev)
@@ -176,22 +132,22 @@ def _device_run(data, tld, rows, n, covariance, ddof, keeptrials):
         cov = (torch.empty if keeptrials else torch.zeros)((T, nchan, nchan) if keeptrials else (nchan, nchan),
                                                           dtype=torch.float32, device=dev)
     kept = None
-    for k0, k1 in spans:
-        x = chunk(k0, k1)
+    for ks in chunks:
+        x, _ = source.gather(ks, n)
         backend.trial_sum(x, acc)
         if covariance and keeptrials:
-            backend.cov(x, ddof, out=cov[k0:k1])
+            backend.cov(x, ddof, out=cov[ks[0]:ks[-1] + 1])
         elif covariance:
             backend.trial_sum(backend.cov(x, ddof), cov)
-        if len(spans) == 1:
+        if len(chunks) == 1:
             kept = x                                # one chunk: pass 2 needs no second upload
     mean = backend.trial_sum_finalize(acc, T)
     if covariance and not keeptrials:
         backend.trial_sum_finalize(cov, T)
     # pass 2: the squared deviations from the trial mean
     sq = torch.zeros((n, nchan), dtype=torch.float32, device=dev)
-    for k0, k1 in spans:
-        backend.trial_sqdev(kept if kept is not None else chunk(k0, k1), mean, sq)
+    for ks in chunks:
+        backend.trial_sqdev(kept if kept is not None else source.gather(ks, n)[0], mean, sq)
     kept = None
     tld.avg = backend.to_host(mean)
     tld.var = backend.to_host(backend.trial_var_finalize(sq, T, torch.float32, False))
@@ -199,9 +155,6 @@ def _device_run(data, tld, rows, n, covariance, ddof, keeptrials):
         tld.cov = backend.to_host(cov).squeeze()
 
     if data._data is not None:
-        tld.data = _host_stack(data, rows, chans)
+        tld.data = source.host_stack()
     else:                                           # the input lives on the device only: fetch the rows when asked for
-        def fetch():
-            parts = [src[a:b] if full else src[a:b].index_select(1, cidx) for a, b in src_rows]
-            return np.concatenate([backend.to_host(p.contiguous()) for p in parts], axis=0)
-        tld.set_pending(fetch, (T * n, nchan), np.float32)
+        tld.set_pending(source.fetch_rows, (T * n, nchan), np.float32)
