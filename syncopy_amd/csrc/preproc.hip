@@ -49,15 +49,6 @@ int fill_sos(const char* who, const double* sos, const double* zi, int nsec, Sos
     return 0;
 }
 
-// run `launch<NS>` for the smallest compiled cascade length that holds nsec sections
-#define SPY_SOS_DISPATCH(nsec, LAUNCH) \
-    do {                               \
-        if ((nsec) <= 2) { LAUNCH(2); } \
-        else if ((nsec) <= 4) { LAUNCH(4); } \
-        else if ((nsec) <= 8) { LAUNCH(8); } \
-        else { LAUNCH(spypre::MAX_SECTIONS); } \
-    } while (0)
-
 }  // namespace
 
 extern "C" int spyhip_detrend(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t ntrials, int64_t nsamp,

@@ -158,6 +158,16 @@ struct SosCoef {
     int nsec;
 };
 
+// run `LAUNCH(NS)` for the smallest compiled cascade length that holds nsec <= MAX_SECTIONS sections (the launchers of
+// preproc.hip and the CPU emulation of the tests both dispatch through this)
+#define SPY_SOS_DISPATCH(nsec, LAUNCH) \
+    do {                               \
+        if ((nsec) <= 2) { LAUNCH(2); } \
+        else if ((nsec) <= 4) { LAUNCH(4); } \
+        else if ((nsec) <= 8) { LAUNCH(8); } \
+        else { LAUNCH(spypre::MAX_SECTIONS); } \
+    } while (0)
+
 // one sample through the cascade, SciPy's _sosfilt statement by statement (transposed direct form II)
 template <int NS>
 __device__ __forceinline__ double sos_step(const SosCoef& k, double (&z)[NS][2], double v) {

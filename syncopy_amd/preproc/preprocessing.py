@@ -32,6 +32,9 @@ availableDirections = ("twopass", "onepass", "onepass-minphase")
 availableWindows = design.WINDOWS
 hilbert_outputs = {"abs", "complex", "real", "imag", "absreal", "absimag", "angle"}
 
+# second-order sections the cascade kernels are compiled for (MAX_SECTIONS of csrc/preproc_kernel.h)
+MAX_SECTIONS = 12
+
 # bytes of input trials filtered at once (the work buffers on the device are a small multiple of this)
 CHUNK_BYTES = 512 << 20
 
@@ -131,6 +134,9 @@ def preprocessing(data, filter_class="but", filter_type="lp", freq=None, order=N
             if order < 1:
                 raise SPYValueError("order of at least 1", varname="order", actual=str(order))
             sos, zi, edge = design.butterworth(order, freq, filter_type, data.samplerate)
+            if sos.shape[0] > MAX_SECTIONS:          # refused here, ahead of any upload: the launchers would refuse too
+                raise SPYValueError(f"a filter of at most {MAX_SECTIONS} second-order sections (order {2 * MAX_SECTIONS} "
+                                    f"for 'lp' / 'hp', {MAX_SECTIONS} for 'bp' / 'bs')", varname="order", actual=str(order))
             if direction == "twopass":
                 if lengths.min() <= edge:
                     raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")

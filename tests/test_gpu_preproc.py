@@ -2,6 +2,12 @@
 same front end, and the ABI wrappers on their own.  Criterion: tests/parity.py per trial.  Detrend order 0 and the z-score
 are compared with the float32 NumPy / SciPy result, the filters and the line fit with the float64 model.
 
+The Butterworth cascade is held to a second bound, element-wise 2^-23 |ref| + 1e-10 max_t |ref| per channel
+(test_preproc.sos_excess): the parity criterion cannot tell a float64 filter state from a float32 one, this bound can.
+Its constant was placed on the CPU between two models (test_preproc.py::test_sos_bound_sits_between_the_models: float64
+with fused against separate multiply-adds 2.7e-13, float32 state at least 2.0e-8; neither figure is a device figure).
+The device's own distance from that bound is what the tests print as "err/bound".
+
 Measured on an MI355X: see DESIGN.md section 8 (whether detrend / z-score are bit-identical is printed by
 test_demean_and_zscore_bits)."""
 import numpy as np
@@ -9,7 +15,9 @@ import pytest
 
 import syncopy_amd as spy
 import preproc_oracle as PO
-from parity import assert_parity, excess
+from parity import ATOL_REL, RTOL, assert_parity, excess
+from syncopy_amd.preproc import design
+from test_preproc import BUT_CASES, BUT_FREQ, but_sections, sos_excess
 
 pytestmark = pytest.mark.gpu
 HOW = dict(compute_method="sequential", routine_classes=PO.PREPROC_OPS)
@@ -27,24 +35,210 @@ def _data(lengths, nchan, seed=0, offset=True):
     return spy.AnalogData(x.astype(np.float32), samplerate=FS, trialdefinition=trl)
 
 
-def _compare(data, what, exact=False, **kw):
+def _compare(data, what, exact=False, tight=False, model_floor=0.0, **kw):
+    """The device against the model through the same front end: the same NaN, +inf and -inf elements, the finite ones at
+    parity per trial.  tight: the Butterworth bound of test_preproc.sos_excess as well.  model_floor: what the float64
+    model's own rounding leaves where the exact result is zero, added to the tolerance (test_detrend_and_zscore_tiny)."""
     got = spy.preprocessing(data, **kw)
     ref = spy.preprocessing(data, **kw, **HOW)
     assert got.data.dtype == np.float32 and got.data.shape == ref.data.shape, what
     assert np.array_equal(np.asarray(got.trialdefinition), np.asarray(ref.trialdefinition)), what
     assert list(got.channel) == list(ref.channel), what
     assert got.info.get("nan_trials") == ref.info.get("nan_trials"), what
-    worst = 0.0
+    worst = bound = 0.0
     for g, r in zip(got.trials, ref.trials):
-        nan = np.isnan(r)
-        assert np.array_equal(np.isnan(g), nan), f"{what}: NaN pattern"
-        if (~nan).any():
-            worst = max(worst, excess(g[~nan], r[~nan]))
-    print(f"{what}: err/tol {worst:.3g}")
+        assert np.array_equal(np.isnan(g), np.isnan(r)), f"{what}: NaN pattern"
+        assert np.array_equal(g == np.inf, r == np.inf), f"{what}: +inf pattern"
+        assert np.array_equal(g == -np.inf, r == -np.inf), f"{what}: -inf pattern"
+        ok = np.isfinite(r)
+        if ok.any() and model_floor:
+            tol = RTOL * np.abs(r[ok]) + ATOL_REL * np.abs(r[ok]).max() + model_floor
+            worst = max(worst, float((np.abs(g[ok].astype(np.float64) - r[ok]) / tol).max()))
+        elif ok.any():
+            worst = max(worst, excess(g[ok], r[ok]))
+        if tight:
+            bound = max(bound, sos_excess(g, r))
+    print(f"{what}: err/tol {worst:.3g}" + (f", err/bound {bound:.3g}" if tight else ""))
     assert worst <= 1.0, f"{what}: err/tol {worst:.3g}"
+    assert bound <= 1.0, f"{what}: err/bound {bound:.3g}"
     if exact:
         print(f"{what}: bit-identical {np.array_equal(got.data, ref.data, equal_nan=True)}")
     return got, ref
+
+
+def _but(data, ftype, order, direction, what, **kw):
+    return _compare(data, f"but {ftype} order {order} ({but_sections(ftype, order)} sections) {direction} {what}", tight=True,
+                    filter_class="but", filter_type=ftype, freq=BUT_FREQ[ftype], order=order, direction=direction, **kw)
+
+
+# ---- the Butterworth cascade at every compiled instance -----------------------------------------------------------
+# NS = 2, 4, 8 and 12 sections are compiled (SPY_SOS_DISPATCH of csrc/preproc_kernel.h); BUT_CASES runs 1 ... 12
+# sections, and each NS once more with RECT = true: 2, 4, 8 and 12 sections
+RECTIFIED = [("lp", 4), ("bp", 4), ("hp", 16), ("lp", 24), ("bs", 12)]
+EVERY = [(f, o, False) for f, o in BUT_CASES] + [(f, o, True) for f, o in RECTIFIED]
+
+
+@pytest.mark.parametrize("direction", ["onepass", "twopass"])
+@pytest.mark.parametrize("ftype,order,rectify", EVERY,
+                         ids=[f"{f}{o}-{but_sections(f, o)}sections" + ("-rect" if r else "") for f, o, r in EVERY])
+def test_butterworth_every_section_count(ftype, order, rectify, direction):
+    edge = design.butterworth(order, BUT_FREQ[ftype], ftype, FS)[2]
+    _but(_data([edge + 9, 333], 5, seed=order), ftype, order, direction, f"rectify={rectify}", rectify=rectify)
+
+
+# 2, 5 (once with a first-order section, which shortens `edge`) and 12 sections
+@pytest.mark.parametrize("ftype,order", [("lp", 3), ("lp", 9), ("bp", 5), ("hp", 24), ("bs", 12)],
+                         ids=lambda v: str(v))
+def test_butterworth_shortest_legal_trial(ftype, order):
+    """nsamp = edge + 1: the odd extension at either end reaches the far end of the trial"""
+    import torch
+    from syncopy_amd import backend
+    sos, zi, edge = design.butterworth(order, BUT_FREQ[ftype], ftype, FS)
+    _but(_data([edge + 1, edge + 2, edge + 1], 5, seed=order), ftype, order, "twopass", f"nsamp = edge + 1 = {edge + 1}")
+    kw = dict(filter_class="but", filter_type=ftype, freq=BUT_FREQ[ftype], order=order, direction="twopass")
+    short = _data([edge + 1, edge], 5, seed=order)
+    with pytest.raises(ValueError, match="padlen"):
+        spy.preprocessing(short, **kw)
+    with pytest.raises(ValueError, match="padlen"):
+        spy.preprocessing(short, **kw, **HOW)
+    xd = torch.zeros((2, edge, 5), dtype=torch.float32, device="cuda")
+    out = torch.full_like(xd, 7.0)
+    with pytest.raises(backend.SpyHipError):
+        backend.sosfiltfilt(xd, out, sos, zi, edge, torch.zeros(2, dtype=torch.int32, device="cuda"))
+    assert (out == 7.0).all().item()
+
+
+@pytest.mark.parametrize("direction", ["onepass", "twopass"])
+def test_butterworth_loop_remainders(direction):
+    """5 sections, trials of 40 ... 47 samples: every remainder of nsamp (one-pass) and of nsamp + 2 * edge (forward and
+    backward pass) modulo LOAD_AHEAD = 8"""
+    _but(_data(list(range(40, 48)), 3, seed=40), "bp", 5, direction, "nsamp 40 ... 47")
+
+
+def _scaled(lengths, nchan, seed):
+    """every channel with an offset and a scale of its own, so that no series can stand in for its neighbour"""
+    data = _data(lengths, nchan, seed=seed, offset=False)
+    rng = np.random.default_rng(seed + 1)
+    scale = np.logspace(-1, 1, nchan)[rng.permutation(nchan)]
+    data.data[:] = (data.data * scale + 3.0 * np.arange(1, nchan + 1)).astype(np.float32)
+    data.invalidate()
+    return data
+
+
+@pytest.mark.parametrize("ftype,order,direction", [("lp", 4, "twopass"), ("bp", 6, "onepass")])
+@pytest.mark.parametrize("nchan", [1, 63, 64, 65])
+def test_butterworth_series_map(nchan, ftype, order, direction):
+    """3 trials x nchan series against the 64 threads of a workgroup (my_series)"""
+    data = _scaled([120, 97, 120], nchan, seed=nchan)
+    got, ref = _but(data, ftype, order, direction, f"nchan={nchan}")
+    series = np.stack([np.asarray(r)[:97].T for r in ref.trials]).reshape(3 * nchan, 97)     # (trial, channel) order
+    for a, b in zip(series[:-1], series[1:]):              # a result stored one series off could not pass
+        assert excess(a, b) > 1.0
+
+
+@pytest.mark.parametrize("direction", ["onepass", "twopass"])
+@pytest.mark.parametrize("ftype,order", [("lp", 24), ("bs", 12)])
+def test_butterworth_12_sections_nan_in_one_channel(ftype, order, direction):
+    edge = design.butterworth(order, BUT_FREQ[ftype], ftype, FS)[2]
+    n = edge + 9
+    data = _data([n, n, n], 9, seed=17)
+    data.data[n + n // 2, 4] = np.nan
+    data.invalidate()
+    with pytest.warns(UserWarning, match="NaN"):
+        got, ref = _but(data, ftype, order, direction, "NaN")          # the model's NaN pattern, all else inside the bounds
+    assert got.info["nan_trials"] == [1]
+    bad = np.isnan(got.data)
+    assert bad[:, [c for c in range(9) if c != 4]].sum() == 0 and bad[:n].sum() == 0 and bad[2 * n:].sum() == 0
+    assert np.isfinite(got.data[~bad]).all()
+    assert bad.sum() == (n - n // 2 if direction == "onepass" else n)
+
+
+def test_detrend_and_onepass_in_place():
+    """"out may be in" (csrc/preproc_kernel.h): the same bits as out of place"""
+    import torch
+    from syncopy_amd import backend
+    x = torch.from_numpy(np.random.default_rng(21).normal(size=(3, 77, 65)).astype(np.float32) + 2.0).cuda()
+    flag = torch.zeros(3, dtype=torch.int32, device="cuda")
+    sos12 = design.butterworth(12, BUT_FREQ["bs"], "bs", FS)[0]
+    sos3 = design.butterworth(5, BUT_FREQ["lp"], "lp", FS)[0]
+    calls = [lambda i, o, r=r, k=k: backend.detrend(i, o, k, flag, r) for k in (0, 1) for r in (False, True)]
+    calls += [lambda i, o, r=r, k=k: backend.sosfilt(i, o, k, flag, r) for k in (sos3, sos12) for r in (False, True)]
+    for call in calls:
+        apart = call(x, torch.empty_like(x)).cpu().numpy()
+        buf = x.clone()
+        assert call(buf, buf) is buf
+        assert np.array_equal(buf.cpu().numpy(), apart)
+    one = x[:, :, :1].contiguous()                         # one channel: detrend order 0 takes NumPy's pairwise sum
+    apart = backend.detrend(one, torch.empty_like(one), 0, flag).cpu().numpy()
+    assert np.array_equal(backend.detrend(one, one, 0, flag).cpu().numpy(), apart)
+    assert not flag.any().item()
+
+
+@pytest.mark.parametrize("kw", [dict(freq=100, order=25), dict(filter_type="hp", freq=30, order=25, direction="onepass"),
+                                dict(filter_type="bp", freq=[20, 80], order=13),
+                                dict(filter_type="bs", freq=[45, 55], order=13, direction="onepass")])
+def test_butterworth_13_sections_are_refused_before_any_device_work(kw, monkeypatch):
+    import importlib
+    import torch
+    from syncopy_amd import backend
+    from syncopy_amd.shared.errors import SPYValueError
+    mod = importlib.import_module("syncopy_amd.preproc.preprocessing")
+    monkeypatch.setattr(mod, "_device_run", lambda *a, **k: (_ for _ in ()).throw(AssertionError("device work")))
+    with pytest.raises(SPYValueError):
+        spy.preprocessing(_data([400, 400], 3, seed=25), **kw)
+    monkeypatch.undo()
+    sos, zi, edge = design.butterworth(kw["order"], kw["freq"], kw.get("filter_type", "lp"), FS)
+    assert sos.shape[0] == 13
+    xd = torch.zeros((2, 400, 3), dtype=torch.float32, device="cuda")
+    out = torch.full_like(xd, 7.0)
+    flag = torch.zeros(2, dtype=torch.int32, device="cuda")
+    with pytest.raises(backend.SpyHipError):
+        backend.sosfilt(xd, out, sos, flag)
+    with pytest.raises(backend.SpyHipError):
+        backend.sosfiltfilt(xd, out, sos, zi, edge, flag)
+    assert (out == 7.0).all().item()
+
+
+# ---- detrend and z-score at tiny shapes ---------------------------------------------------------------------------
+TINY = (1, 2, 7, 8, 9, 16, 17)
+
+
+def _tiny(nchan):
+    """three trials of every length of TINY; the first holds a constant channel (2.5: its mean is exact, the z-score
+    0 / 0), the second one of 0.1 (the float32 mean may miss it), the third one of +-1e-30 in turn (its squares underflow,
+    standard deviation 0, the z-score +-inf).  One sample per trial gives 0 / 0 everywhere."""
+    lengths = [n for n in TINY for _ in range(3)]
+    data = _data(lengths, nchan, seed=nchan, offset=False)
+    data.data[:] += np.random.default_rng(nchan).normal(size=(1, nchan)).astype(np.float32)
+    row = 0
+    for n in TINY:
+        data.data[row:row + n, 0] = 2.5
+        data.data[row + n:row + 2 * n, nchan - 1] = np.float32(0.1)
+        data.data[row + 2 * n:row + 3 * n, 0] = np.float32(1e-30) * (1 - 2 * (np.arange(n) % 2))
+        row += 3 * n
+    data.invalidate()
+    return data
+
+
+@pytest.mark.parametrize("rectify", [False, True])
+@pytest.mark.parametrize("kw", [dict(polyremoval=0), dict(polyremoval=1), dict(zscore=True), dict(polyremoval=0, zscore=True)],
+                         ids=lambda kw: "-".join(f"{k}{int(v)}" for k, v in kw.items()))
+@pytest.mark.parametrize("nchan", [1, 2, 64, 65])
+def test_detrend_and_zscore_tiny(nchan, kw, rectify):
+    """nsamp 1, 2, 7, 8, 9, 16, 17 (LOAD_AHEAD = 8, NumPy's pairwise blocks of 8 with one channel) x nchan 1, 2, 64, 65.
+
+    Where the least-squares line meets every sample (one or two samples, a constant channel) the exact result is 0: the
+    kernel returns 0, the float64 model what its own rounding leaves (3e-15 at most on these data with the kernel's CPU
+    emulation, for samples of size 5: a few 2^-53 of the sample; not a device figure).  The line fit is therefore given
+    2^-44 max|x| on top of the parity tolerance: a hundred times that residue, and 1e-6 of the last bit a float32
+    result of the samples' size has."""
+    data = _tiny(nchan)
+    floor = 2.0 ** -44 * float(np.abs(data.data).max()) if kw.get("polyremoval") == 1 else 0.0
+    got, ref = _compare(data, f"tiny c={nchan} {kw} rectify={rectify}", model_floor=floor, filter_class=None, rectify=rectify, **kw)
+    if kw.get("zscore"):
+        odd = ~np.isfinite(ref.data)
+        assert np.isnan(ref.data).any() and np.isinf(ref.data).any()
+        assert np.array_equal(got.data[odd], ref.data[odd], equal_nan=True)
 
 
 @pytest.mark.parametrize("ftype,freq", [("lp", 100), ("hp", 30), ("bp", [20, 80]), ("bs", [45, 55])])

@@ -92,7 +92,9 @@ def _edge_data(rng, shape, cplx):
 @pytest.mark.parametrize("cplx", [False, True])
 @pytest.mark.parametrize("shape,axis", [((1, 4), 0), ((2, 3), 0), ((3, 5), 0), ((599, 3), 0), ((600, 2), 0),
                                         ((601, 3), 0), ((7, 1200), 1), ((100000, 2), 0), ((3, 100000), 1),
-                                        ((40, 9000), 1), ((5, 33, 70), 1)])
+                                        ((40, 9000), 1), ((5, 33, 70), 1)] +
+                         # MED_STAGE_BYTES = 32768: a slice's keys stay in LDS up to 8192 float32 / 4096 complex64 elements
+                         [(s, a) for n in (4095, 4096, 4097, 8191, 8192, 8193) for s, a in (((n, 3), 0), ((3, n), 1))])
 def test_device_axis_edge_slices(cplx, shape, axis):
     import torch
     from syncopy_amd import backend

@@ -7,6 +7,9 @@ the float64 dot-product error bound at these lengths.  The parity criterion alon
 a float32 one (on the CPU, float32 accumulation sits at 0.02 ... 0.05 of its tolerance); the second bound can (float32
 accumulation exceeds it 5 ... 18 times).
 
+The second half of the file calls backend.cov itself at the edges of its tiling (csrc/cov_kernel.h: 16 x 16 tiles in
+64 x 64 blocks, chunks of COV_KC = 32 rows of which a matrix instruction takes 4, MAX_Z = 65535 trials per launch).
+
 Measured on an MI355X (tools/timelock_bench.py): see DESIGN.md section 8."""
 import importlib
 
@@ -22,15 +25,34 @@ pytestmark = pytest.mark.gpu
 HOW = dict(compute_method="sequential", routine_classes=TO.TIMELOCK_OPS)
 
 
-def _data(ntrials, n, nchan, seed=0, dc=0.0, fs=1000.0, offset=-100):
-    """channel scales from 1e-2 to 1e2, correlated channels, a mean of its own per channel and trial"""
+def _batch(ntrials, n, nchan, seed=0, dc=0.0):
+    """(ntrials, n, nchan) float32: channel scales from 1e-2 to 1e2, correlated channels, a mean of its own per channel
+    and trial - a transposed or shifted tile of the covariance cannot pass"""
     rng = np.random.default_rng(seed)
     mix = rng.normal(size=(nchan, nchan)) / np.sqrt(nchan) + np.eye(nchan)
     x = rng.normal(size=(ntrials, n, nchan)) @ mix
     x = x * np.logspace(-2, 2, nchan)[rng.permutation(nchan)] + rng.normal(size=(ntrials, 1, nchan)) + dc
+    return x.astype(np.float32)
+
+
+def _data(ntrials, n, nchan, seed=0, dc=0.0, fs=1000.0, offset=-100):
     e = np.arange(ntrials + 1) * n
     trl = np.stack([e[:-1], e[1:], np.full(ntrials, float(offset))], axis=1)
-    return spy.AnalogData(x.reshape(ntrials * n, nchan).astype(np.float32), samplerate=fs, trialdefinition=trl)
+    return spy.AnalogData(_batch(ntrials, n, nchan, seed, dc).reshape(ntrials * n, nchan), samplerate=fs, trialdefinition=trl)
+
+
+def _device_cov(x, ddof=None):
+    import torch
+    from syncopy_amd import backend
+    return backend.cov(torch.from_numpy(x).cuda(), ddof=ddof).cpu().numpy()
+
+
+def _check_cov(x, ddof, what):
+    got = _device_cov(x, ddof)
+    ref = np.stack([TO.cov(t, ddof) for t in x])
+    assert_cov(got, ref, what=what)
+    assert np.array_equal(got, got.transpose(0, 2, 1), equal_nan=True), f"{what}: symmetry"
+    return got, ref
 
 
 def _compare(data, what, **kw):
@@ -187,3 +209,49 @@ def test_abi_wrapper_directly():
         assert np.array_equal(dev.cov(x), backend.cov(xd).cpu().numpy())
     finally:
         dev.close()
+
+
+# ---- backend.cov at tile, block and chunk edges --------------------------------------------------------------------
+# tile edges 15/16/17, 31/32/33, 47/48/49; block edges 63/64/65, 127/128/129; 129 channels are three block rows, the
+# last with one channel, 257 and 300 five (the walk from the block index to (bi, bj) goes up to bi = 4)
+@pytest.mark.parametrize("nchan", [15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 127, 128, 129, 257, 300])
+def test_cov_channel_counts_at_tile_and_block_edges(nchan):
+    _check_cov(_batch(2, 65, nchan, seed=nchan), None, f"backend.cov c={nchan} n=65")
+
+
+# shorter than one chunk of 32 rows, at it and next to it, two chunks; 2, 3, 5: zero-filled rows in a matrix instruction
+@pytest.mark.parametrize("n", [2, 3, 4, 5, 31, 32, 33, 63, 64, 65])
+def test_cov_trial_lengths_at_chunk_edges(n):
+    x = _batch(2, n, 70, seed=n)
+    for ddof in sorted({0, 1, n - 1}):
+        _check_cov(x, ddof, f"backend.cov c=70 n={n} ddof={ddof}")
+
+
+def test_cov_of_one_sample_is_zero():
+    got = _device_cov(_batch(2, 1, 70, seed=1), ddof=0)
+    assert got.shape == (2, 70, 70) and not got.any() and not np.signbit(got).any()
+
+
+def test_cov_65537_trials_second_launch():
+    """MAX_Z = 65535 trials go into one launch: trials 65535 and 65536 are the second one's, which offsets x and out"""
+    x = _batch(65537, 2, 3, seed=65537)
+    got = _device_cov(x)
+    d = x.astype(np.float64) - x.astype(np.float64).mean(axis=1, keepdims=True)
+    ref = np.einsum("tki,tkj->tij", d, d).astype(np.float32)               # n - ddof = 1
+    assert_cov(got, ref, what="65537 trials")
+    assert np.array_equal(got, got.transpose(0, 2, 1))
+    for t in (0, 65534, 65535, 65536):
+        assert_cov(got[t], TO.cov(x[t]), what=f"trial {t} of 65537")
+
+
+def test_cov_nan_across_a_block_edge():
+    x = _batch(3, 65, 130, seed=130)
+    x[0, 7, 63] = np.nan
+    x[1, 64, 64] = np.nan
+    x[2, 0, 63] = x[2, 33, 64] = np.nan
+    got, _ = _check_cov(x, None, "NaN in channels 63 and 64")
+    for t, bad in ((0, [63]), (1, [64]), (2, [63, 64])):
+        mask = np.zeros((130, 130), dtype=bool)
+        mask[bad, :] = True
+        mask[:, bad] = True
+        assert np.array_equal(np.isnan(got[t]), mask), t

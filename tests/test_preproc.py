@@ -118,6 +118,10 @@ def test_select_cfg_and_nan_trials():
     (dict(freq=10, rectify=True, hilbert="abs"), SPYValueError), (dict(freq=10, hilbert="phase"), SPYValueError),
     (dict(filter_class=None), SPYValueError), (dict(freq=10, foo=1), SPYValueError),
     (dict(freq=10, hilbert="abs"), NotImplementedError),
+    # 13 second-order sections: one more than the kernels are compiled for (MAX_SECTIONS of csrc/preproc_kernel.h)
+    (dict(freq=100, order=25), SPYValueError), (dict(filter_type="hp", freq=30, order=26, direction="onepass"), SPYValueError),
+    (dict(filter_type="bp", freq=[20, 80], order=13), SPYValueError),
+    (dict(filter_type="bs", freq=[45, 55], order=13, direction="onepass"), SPYValueError),
 ])
 def test_argument_errors(kw, exc):
     with pytest.raises(exc):
@@ -155,6 +159,7 @@ def emu():
     lib.emu_standardize.argtypes = [vp, vp, i, i, i, i, vp]
     lib.emu_sosfilt.argtypes = [vp, vp, i, i, i, vp, i, i, vp]
     lib.emu_sosfiltfilt.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, vp]
+    lib.model_sosfilt.argtypes = [vp, vp, vp, i, i, vp, vp, i, i, i]
     lib.emu_fir_same.argtypes = [vp, vp, i, i, i, vp, i, i, vp]
     return lib
 
@@ -189,21 +194,108 @@ def test_emu_detrend_and_standardize(emu, shape):
         assert_parity(out[t][ok], ref[ok], what="line fit")
 
 
-@pytest.mark.parametrize("ftype,freq,order", [("lp", 100, 4), ("bp", [20, 80], 4), ("bs", [45, 55], 3), ("hp", 30, 6)])
+# ---- the Butterworth cascade: cases and the bound that tells a float64 state from a float32 one -------------------
+# (shared with tests/test_gpu_preproc.py)
+BUT_FREQ = {"lp": 100, "hp": 30, "bp": [20, 80], "bs": [45, 55]}
+# (filter type, order): every section count 1 ... 12, the dispatch boundaries 2|3, 4|5, 8|9 from both sides, odd orders
+# (a first-order section, for which design.butterworth shortens `edge`)
+BUT_CASES = [(f, o) for f in ("lp", "hp") for o in (1, 2, 3, 4, 5, 8, 9, 16, 17, 24)] + \
+            [(f, o) for f in ("bp", "bs") for o in (1, 2, 4, 5, 8, 9, 12)]
+SOS_C = 1e-10
+
+
+def but_sections(ftype, order):
+    return (order + 1) // 2 if ftype in ("lp", "hp") else order
+
+
+def sos_excess(got, ref):
+    """max over the finite elements of `ref` of |got - ref| / (2^-23 |ref| + SOS_C max_t |ref|), the maximum over time
+    taken per channel of the (time, channel) trial: one float32 rounding of the result plus SOS_C of the series' scale.
+    test_sos_bound_sits_between_the_models places SOS_C."""
+    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    fin = np.isfinite(ref)
+    a = np.where(fin, np.abs(ref), 0.0)
+    bound = 2.0 ** -23 * a + SOS_C * a.max(axis=0, keepdims=True)
+    err = np.where(fin, np.abs(np.where(fin, got, 0.0) - np.where(fin, ref, 0.0)), 0.0)
+    return float((err / np.maximum(bound, np.finfo(np.float64).tiny)).max()) if err.size else 0.0
+
+
+def but_trials(lengths, nchan, seed):
+    """float32 (time, channel) trials: noise plus an offset and a ramp of its own per channel"""
+    rng = np.random.default_rng(seed)
+    total = int(np.sum(lengths))
+    x = rng.normal(size=(total, nchan)) + rng.normal(size=(1, nchan))
+    x += np.linspace(0, 1.5, total)[:, None] * rng.normal(size=(1, nchan))
+    e = np.concatenate([[0], np.cumsum(lengths)])
+    return [x[a:b].astype(np.float32) for a, b in zip(e[:-1], e[1:])]
+
+
+def _model(emu, x, sos, zi, edge, how):
+    """(float32 result, unrounded float64 result) of the plain cascade `how` of tests/emu/preproc_emu.cpp"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out, out64 = np.empty_like(x), np.empty(x.shape)
+    assert emu.model_sosfilt(_p(x), _p(out), _p(out64), *x.shape, _p(sos), _p(zi), sos.shape[0], edge, how) == 0
+    return out, out64
+
+
+def test_sos_bound_sits_between_the_models(emu):
+    """Where SOS_C of sos_excess() comes from.  Over every case of BUT_CASES, one-pass and two-pass, on the trials the
+    device test uses (edge + 9 and 333 samples, 5 channels), all on the CPU (nothing here is measured on the device):
+
+    (a) the float64 cascade with its multiply-adds fused, in either pairing a compiler may choose, against the same
+        cascade with separate operations (which is scipy.signal.sosfilt / sosfiltfilt bit for bit, asserted here):
+        the unrounded results differ by at most 2.7e-13 of the series' largest value;
+    (b) the same cascade with the state z kept in float32 exceeds the float32 rounding of the result, 2^-23 |ref|, by
+        2.0e-8 of the series' largest value in the mildest case and by more in every other.
+
+    SOS_C = 1e-10 lies 370 times above (a) and 200 times below (b); a factor 10 on either side is asserted, and so is
+    that sos_excess() refuses the float32 state on every single trial."""
+    worst_a, least_b = 0.0, np.inf
+    for ftype, order in BUT_CASES:
+        sos, zi, edge = design.butterworth(order, BUT_FREQ[ftype], ftype, 1000.0)
+        assert sos.shape[0] == but_sections(ftype, order)
+        for e, oracle in ((-1, PO.sosfilt), (edge, PO.sosfiltfilt)):
+            b = 0.0
+            for x in but_trials([edge + 9, 333], 5, seed=order):
+                ref = oracle(x, sos).astype(np.float64)
+                scale = np.abs(ref).max(axis=0, keepdims=True)
+                plain, plain64 = _model(emu, x, sos, zi, e, 0)
+                assert np.array_equal(plain, ref), (ftype, order, e)
+                for how in (1, 2):
+                    worst_a = max(worst_a, float((np.abs(_model(emu, x, sos, zi, e, how)[1] - plain64) / scale).max()))
+                f32 = _model(emu, x, sos, zi, e, 3)[0]
+                b = max(b, float(((np.abs(f32 - ref) - 2.0 ** -23 * np.abs(ref)) / scale).max()))
+                assert sos_excess(f32, ref) > 1.0, (ftype, order, e)            # the bound sees a float32 state
+            least_b = min(least_b, b)
+    print(f"(a) fused against separate float64: {worst_a:.3g}; (b) float32 state, least over the cases: {least_b:.3g}")
+    assert 10 * worst_a <= SOS_C <= least_b / 10
+
+
+# 2, 4, 2 and 3 sections (NS = 2, 4, 2, 4); 6 (NS = 8); 9 and 12, twice (NS = MAX_SECTIONS), the last with a narrow stop band
+@pytest.mark.parametrize("ftype,freq,order", [("lp", 100, 4), ("bp", [20, 80], 4), ("bs", [45, 55], 3), ("hp", 30, 6),
+                                              ("bp", [20, 80], 6), ("lp", 100, 17), ("hp", 30, 24), ("bs", [45, 55], 12)])
 def test_emu_sos(emu, ftype, freq, order):
-    shape = (2, 200, 3)
-    x = _batch(*shape, seed=2)
     sos, zi, edge = design.butterworth(order, freq, ftype, 1000.0)
     flag = np.zeros(2, np.int32)
-    out = np.empty_like(x)
-    emu.emu_sosfilt(_p(x), _p(out), *shape, _p(sos), sos.shape[0], 0, _p(flag))
-    for t in range(2):
-        assert_parity(out[t], PO.sosfilt(x[t], sos), what="sosfilt")
-    work = np.empty((2, 200 + 2 * edge, 3))
-    emu.emu_sosfiltfilt(_p(x), _p(out), _p(work), *shape, _p(sos), _p(zi), sos.shape[0], edge, 1, _p(flag))
-    for t in range(2):
-        assert_parity(out[t], np.abs(PO.sosfiltfilt(x[t], sos)), what="sosfiltfilt")
-    assert not flag.any()
+    for nsamp in (200, edge + 1):                           # edge + 1: the shortest trial sosfiltfilt takes
+        shape = (2, nsamp, 3)
+        x = _batch(*shape, seed=2)
+        out = np.empty_like(x)
+        assert emu.emu_sosfilt(_p(x), _p(out), *shape, _p(sos), sos.shape[0], 0, _p(flag)) == 0
+        for t in range(2):
+            ref = PO.sosfilt(x[t], sos)
+            assert_parity(out[t], ref, what="sosfilt")
+            assert sos_excess(out[t], ref) <= 1.0
+        work = np.empty((2, nsamp + 2 * edge, 3))
+        assert emu.emu_sosfiltfilt(_p(x), _p(out), _p(work), *shape, _p(sos), _p(zi), sos.shape[0], edge, 1, _p(flag)) == 0
+        for t in range(2):
+            ref = np.abs(PO.sosfiltfilt(x[t], sos))
+            assert_parity(out[t], ref, what="sosfiltfilt")
+            assert sos_excess(out[t], ref) <= 1.0
+        assert not flag.any()
+    # a trial of exactly `edge` samples and a 13th section are refused, as by the launchers
+    assert emu.emu_sosfiltfilt(_p(x), _p(out), _p(work), 2, edge, 3, _p(sos), _p(zi), sos.shape[0], edge, 1, _p(flag)) == -1
+    assert emu.emu_sosfilt(_p(x), _p(out), *shape, _p(sos), 13, 0, _p(flag)) == -1
 
 
 @pytest.mark.parametrize("N,Cn,ntaps", [(40, 3, 9), (33, 65, 17), (8, 2, 25), (23, 1, 8 + 1), (16, 4, 41)])
