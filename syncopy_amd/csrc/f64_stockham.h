@@ -3,14 +3,9 @@
 // lengths the radix-16 register kernel does not serve (mtmfft_f64_kernel.h).
 #pragma once
 #include "cd_math.h"
+#include "f64_plus_plan.h"   // PlusPlan, plus_plan
 
 namespace spywil {
-
-constexpr int PO_MAXFAC = 24;
-struct PlusPlan {
-    int L, nfac;
-    int radix[PO_MAXFAC];
-};
 
 __device__ __forceinline__ void po_pass(const cd* in, cd* out, int L, int R, int Ns, const cd* tw, int sign, int tid) {
     // tw[m] = exp(-2 pi i m / L); sign = -1 forward, +1 inverse (conjugated twiddles)
@@ -127,19 +122,6 @@ __device__ __forceinline__ void po_pass_any(const cd* in, cd* out, int L, int R,
     else if (R == 3) po_pass_small<3>(in, out, L, Ns, tw, sign, tid);
     else if (R == 7) po_pass_small<7>(in, out, L, Ns, tw, sign, tid);
     else po_pass(in, out, L, R, Ns, tw, sign, tid);
-}
-
-// factors of L in the order the passes take them: 4, 2, 3, 5, 7, 11, 13, then the remaining primes
-inline bool plus_plan(int L, PlusPlan* pl) {
-    pl->L = L;
-    int k = 0, n = L;
-    static const int cand[] = {4, 2, 3, 5, 7, 11, 13};
-    for (int c : cand)
-        while (n % c == 0 && n > 1) { if (k >= PO_MAXFAC) return false; pl->radix[k++] = c; n /= c; }
-    for (int p = 17; n > 1; p += 2)
-        while (n % p == 0) { if (k >= PO_MAXFAC) return false; pl->radix[k++] = p; n /= p; }
-    pl->nfac = k;
-    return true;
 }
 
 }  // namespace spywil

@@ -16,14 +16,9 @@ static int declong64_post(hipStream_t stream, const Long64Args& a, int M) {
 
 template <int P>
 static int declong64_post_mode(hipStream_t stream, const Long64Args& a, int M, int outk, bool mean) {
-    switch (outk * 2 + (mean ? 1 : 0)) {
-        case 0: return declong64_post<P, 0, false>(stream, a, M);
-        case 1: return declong64_post<P, 0, true>(stream, a, M);
-        case 2: return declong64_post<P, 1, false>(stream, a, M);
-        case 3: return declong64_post<P, 1, true>(stream, a, M);
-        case 4: return declong64_post<P, 2, false>(stream, a, M);
-        default: return declong64_post<P, 2, true>(stream, a, M);
-    }
+    return spy::dispatch_mode(outk, mean, [&](auto K, auto Mn) {
+        return declong64_post<P, decltype(K)::value, decltype(Mn)::value>(stream, a, M);
+    });
 }
 
 int declong64_launch_post(hipStream_t stream, const Long64Args& a, int P, int M, int outk, bool mean) {

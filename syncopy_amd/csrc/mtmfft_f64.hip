@@ -21,15 +21,9 @@ int f64_any_launch(hipStream_t stream, F64Args a, long long grid, long long chun
     for (long long w0 = 0; w0 < grid; w0 += chunk) {
         a.wg0 = w0;
         const unsigned g = (unsigned)std::min(chunk, grid - w0);
-        int rc;
-        switch (outk * 2 + (mean ? 1 : 0)) {
-            case 0: rc = f64_any_launch_one<0, false>(stream, a, g); break;
-            case 1: rc = f64_any_launch_one<0, true>(stream, a, g); break;
-            case 2: rc = f64_any_launch_one<1, false>(stream, a, g); break;
-            case 3: rc = f64_any_launch_one<1, true>(stream, a, g); break;
-            case 4: rc = f64_any_launch_one<2, false>(stream, a, g); break;
-            default: rc = f64_any_launch_one<2, true>(stream, a, g); break;
-        }
+        const int rc = spy::dispatch_mode(outk, mean, [&](auto K, auto Mn) {
+            return f64_any_launch_one<decltype(K)::value, decltype(Mn)::value>(stream, a, g);
+        });
         if (rc) return rc;
     }
     return 0;

@@ -20,14 +20,9 @@ int launch(hipStream_t stream, const spyfft::MtmArgs& a, const spyfft::MixPlan& 
 template <int LB>
 int launch_mode(hipStream_t stream, const spyfft::MtmArgs& a, const spyfft::MixPlan& g, int threads, size_t lds, unsigned grid,
                 int outk, bool mean) {
-    switch (outk * 2 + (mean ? 1 : 0)) {
-        case 0: return launch<0, false, LB>(stream, a, g, threads, lds, grid);
-        case 1: return launch<0, true, LB>(stream, a, g, threads, lds, grid);
-        case 2: return launch<1, false, LB>(stream, a, g, threads, lds, grid);
-        case 3: return launch<1, true, LB>(stream, a, g, threads, lds, grid);
-        case 4: return launch<2, false, LB>(stream, a, g, threads, lds, grid);
-        default: return launch<2, true, LB>(stream, a, g, threads, lds, grid);
-    }
+    return spy::dispatch_mode(outk, mean, [&](auto K, auto Mn) {
+        return launch<decltype(K)::value, decltype(Mn)::value, LB>(stream, a, g, threads, lds, grid);
+    });
 }
 }  // namespace
 

@@ -62,11 +62,11 @@ CASES = [
     (5003, 5003, 6, "dpss", {"NW": 3, "Kmax": 3}, "pow", False, 1, True),             # prime
     (11000, 11000, 4, "hann", {}, "fourier", True, 0, False),
     (5000, 5000, 6, "dpss", {"NW": 3, "Kmax": 3}, "pow", False, 1, True),             # 8*5^4: mixed-radix LDS kernel
-    (32768, 32768, 3, "dpss", {"NW": 2, "Kmax": 2}, "pow", False, 0, False),           # power of two: plain four-step
+    (32768, 32768, 3, "dpss", {"NW": 2, "Kmax": 2}, "pow", False, 0, False),           # power of two: declong<8 x 4096>
     (30000, 30000, 5, "dpss", {"NW": 2, "Kmax": 2}, "abs", True, 0, False),
     (20000, 32768, 2, "hann", {}, "pow", True, None, False),
     # 10240 < N <= 20480: channel PAIRS through the compile-time schedule of N / 2 (CfgD::HALF, mtmfft_dec_{m,n}.hip);
-    # the reference-precision twins of these lengths stay on N = P M through HBM
+    # the reference-precision twins of these lengths are HALF schedules too (single channels, CfgD64::HALF)
     (12000, 12000, 6, "dpss", {"NW": 3, "Kmax": 3}, "fourier", True, 1, True),        # 3 x 2000 pairs, line fit, demean_taper
     (12288, 12288, 5, "dpss", {"NW": 2, "Kmax": 2}, "pow", False, 0, False),          # 3 x 2048, odd channel count
     (15000, 15000, 7, "hann", {}, "abs", True, 0, False),                              # 3 x 2500
