@@ -202,6 +202,10 @@ int spyhip_csd_accumulate(spyhip_ctx* ctx, const void* spec_d, int64_t nrows, in
  * summed directly like the reference's complex64 products (connectivity/csd.py:98-102) - what the front ends select
  * for output = "imag" / "angle".  Per context; costs ~25 % of K4's throughput at 256 channels. */
 int spyhip_csd_set_phase_exact(spyhip_ctx* ctx, int on);
+/* Name of the dominant kernel an update of `nchan` channels launches on this context (blocked: through
+ * spyhip_csd_accumulate_blocked, else through spyhip_csd_accumulate_split), written to buf[cap]; for rocprof matching.
+ * Follows spyhip_csd_set_phase_exact and SPYHIP_CSD_F32. */
+int spyhip_csd_kernel_name(spyhip_ctx* ctx, int nchan, int blocked, char* buf, int cap);
 /* The same accumulation on the HALF-PRECISION matrix cores (K4h, csrc/csdh_kernel.h) for nchan = 256: every float32
  * operand, scaled by a power of two per channel, is split once into an fp16 pair hi + lo (22 significant bits) and a
  * real product is hi hi' + hi lo' + lo hi' with float32 accumulation - float32-class products at 5.3 x less matrix time

@@ -634,7 +634,7 @@ def csd_accumulate(spec, acc, blocked=False, absmax=None, split=True, ranges=Non
     if Cn == 256 and nrows > 0 and split:
         if absmax is not None:
             assert absmax.is_cuda and absmax.dtype == torch.float32 and absmax.numel() == 256 and absmax.is_contiguous()
-        if ranges and absmax is not None and nrows >= 1024 and not os.environ.get("SPYHIP_CSD_F32"):
+        if ranges and absmax is not None and nrows >= 1024 and "SPYHIP_CSD_F32" not in os.environ:
             # (small batches - a recording consumed chunk by chunk behind its upload - stay in one piece: eight launches of
             # a few hundred rows each cost more than the pipeline gives a call that waits for the bus anyway)
             # frequency range by frequency range, an event behind each: whoever turns the accumulator into a result can
@@ -753,26 +753,13 @@ def csd_split_fallbacks(device=None):
 
 
 def csd_kernel_name(nchan, blocked=False):
-    """Name of the csd_accum_kernel instance spyhip_csd_accumulate launches for `nchan` channels (launch policy of
-    csrc/csd.hip), for matching rocprofv3 rows."""
-    nt = (nchan + 31) // 32
-    ntiles = nt * (nt + 1) // 2
-    import os
-    if nchan == 256 and not blocked and not os.environ.get("SPYHIP_CSD_F32"):
-        return "spycsd::csdh_kernel"
-    if nchan == 256:
-        return "spycsd::csd3m_kernel<256, 8, true, false, false>"
-    if nchan <= 512 and not blocked:
-        return "spycsd::csd3m_kernel<%d, 8, false>" % ((nchan + 15) // 16 * 16)
-    if nchan > 512 and not blocked:
-        return "spycsd::csd3m_kernel<512, 8, false, true> (+ csd3m_kernel<256, 8, false> per 256-channel block)"
-    if not blocked and nchan <= 256:
-        return "spycsd::csd_accum_kernel<5, 4, %d>" % (1 if nchan == 256 else 2)
-    if not blocked and nchan <= 512:
-        return "spycsd::csd_accum_kernel<5, 4, 3>"
-    if ntiles >= 21:
-        return "spycsd::csd_accum_kernel<5, 4, 0>"
-    return "spycsd::csd_accum_kernel<3, 2, 0>" if ntiles >= 6 else "spycsd::csd_accum_kernel<1, 1, 0>"
+    """Name of the dominant kernel csd_accumulate launches for `nchan` channels on the current device's context
+    (spyhip_csd_kernel_name: the launch policy of csrc/csd_route.h), for matching rocprofv3 rows.  Inside
+    `with csd_phase_exact():` it names the 4-multiplication kernels that then run."""
+    ctx = context()
+    buf = C.create_string_buffer(160)
+    check(ctx.lib.spyhip_csd_kernel_name(ctx.handle, int(nchan), int(bool(blocked)), buf, len(buf)), "spyhip_csd_kernel_name")
+    return buf.value.decode()
 
 
 _lib_comm = {}          # device index -> identity of the process group the library's RCCL communicator was built under

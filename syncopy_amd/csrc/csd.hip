@@ -1,87 +1,77 @@
 // Host side of K4/K5: cross-spectral accumulation, finalisation and coherence
-// normalisation (spyhip_csd_accumulate / spyhip_csd_finalize / spyhip_coh_normalize).
+// normalisation (spyhip_csd_accumulate / spyhip_csd_finalize / spyhip_coh_normalize).  Which kernels an update takes is
+// decided in csd_route.h; this file launches the steps of a route.
 #include <algorithm>
 
 #include <cstdlib>
 
 #include "spy_common.h"
+#include "csd_route.h"
 #include "csd_kernel.h"
 #include "csd3m_launch.h"
 #include "csdh_launch.h"
 
 using spycsd::CsdArgs;
+using spycsd::CsdStep;
+using spycsd::StepKind;
+
+static_assert(spycsd::ACCUM_CHUNK_BYTES == (size_t)spycsd::CSD_THREADS * spycsd::CSD_PF * sizeof(float2),
+              "csd_route.h: a chunk holds at most 512 threads x CSD_PF staged elements");
 
 namespace {
 
+// SPYHIP_CSD_F32 in the environment (any value, the empty one included): 256 channels stay on the float32 kernels
+bool env_f32() {
+    static const bool on = std::getenv("SPYHIP_CSD_F32") != nullptr;
+    return on;
+}
+
 template <int TA, int TB, int FAST = 0>
-int launch_accum(spyhip_ctx* ctx, CsdArgs a, long long item_base, long long item_end, int nsplit = 1) {
+int launch_accum(spyhip_ctx* ctx, CsdArgs a, const CsdStep& s) {
     auto kern = spycsd::csd_accum_kernel<TA, TB, FAST>;
-    const int per = 4 * (TA + TB);
-    // frequencies a workgroup can touch: items [i0, i0+per) span at most this many f
-    int nfb = (per + a.ntiles - 1) / a.ntiles;
-    if (per % a.ntiles != 0 && a.ntiles > 1) nfb += 1;
-    if (nfb > a.F) nfb = a.F;
-    const size_t rowbytes = (size_t)nfb * a.cpad * sizeof(float2);
-    // a chunk holds at most 512 threads x CSD_PF staged elements; LDS holds three chunks
-    const size_t chunk_max = (size_t)spycsd::CSD_THREADS * spycsd::CSD_PF * sizeof(float2);
-    int kb = 32;
-    while (kb > 4 && (size_t)kb * rowbytes > chunk_max) kb -= 4;
-    if (!FAST && ((size_t)kb * rowbytes > chunk_max || 3 * (size_t)kb * rowbytes > ctx->lds_per_block)) {
-        spy::set_error("csd_accumulate: %d channels do not fit the LDS staging buffer", a.C);
-        return -3;
-    }
-    const long long rows_wg = nsplit > 1 ? a.rows_per_split : a.nrows;
-    if (kb > rows_wg && !FAST) kb = (int)((rows_wg + 3) & ~3LL);
-    if (FAST) kb = 16;                                   // three 32 KiB buffers of 16 rows x 256 elements
-    a.kb = kb;
-    a.item_base = item_base;
-    a.item_end = item_end;
-    // FAST: + one row of slack - a tile's columns past the last frequency of a row are read (and never stored)
-    const size_t lds = FAST ? 3 * (size_t)16 * 256 * sizeof(float2) + 512 : 3 * (size_t)kb * rowbytes;
+    a.kb = s.geo.kb;
     SPY_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long long wg_items = FAST ? a.fast_per : per;
-    long long grid = (item_end - item_base + wg_items - 1) / wg_items;
-    if (FAST == 3) grid = ((item_end - item_base) / a.ntiles) * a.fast_nwgf;     // whole frequencies x workgroups each
-    if (grid <= 0) return 0;
-    if (grid > 0x7fffffffLL) { spy::set_error("csd_accumulate: grid too large"); return -1; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)nsplit), dim3(spycsd::CSD_THREADS), lds, ctx->stream, a);
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.geo.lds));
+    if (s.geo.grid <= 0) return 0;
+    hipLaunchKernelGGL(kern, dim3((unsigned)s.geo.grid, (unsigned)s.split.nsplit), dim3(spycsd::CSD_THREADS), s.geo.lds,
+                       ctx->stream, a);
     SPY_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-// The workgroups beyond the last full round of a launch, re-cut: 1 tile per wave AND the rows split over blockIdx.y, so
-// that the short workgroups fill the chip once; splits > 0 leave partial sums in library scratch that a fixed-order
-// reduction adds afterwards (deterministic, no atomics).  `first` = first item of the tail.
-int launch_tail(spyhip_ctx* ctx, CsdArgs a, long long first, int64_t nrows, int nfreq, int nchan) {
-    const long long tail_wg = (a.nitems - first + 7) / 8;
-    long long nsplit = ctx->num_cu / tail_wg;
-    const long long max_split = (nrows + 63) / 64;          // at least 64 rows per split
-    if (nsplit > max_split) nsplit = max_split;
-    // the partial sums of the splits are reduced per whole frequency from f0 on: the tail must start on a
-    // frequency boundary (always true on the fast paths, whose items per workgroup are a multiple of ntiles; the
-    // (5,4) path of the blocked layout has 36 whatever ntiles is)
-    if (nsplit < 2 || first % a.ntiles != 0) return launch_accum<1, 1>(ctx, a, first, a.nitems);
-    const int f0 = (int)(first / a.ntiles), nf = nfreq - f0;
-    const size_t need = (size_t)(nsplit - 1) * nf * nchan * nchan * sizeof(float2);
+int launch_accum(spyhip_ctx* ctx, const CsdArgs& a, const CsdStep& s) {
+    switch (s.ta * 10 + s.fast) {
+        case 50: return launch_accum<5, 4>(ctx, a, s);
+        case 51: return launch_accum<5, 4, 1>(ctx, a, s);
+        case 52: return launch_accum<5, 4, 2>(ctx, a, s);
+        case 53: return launch_accum<5, 4, 3>(ctx, a, s);
+        case 30: return launch_accum<3, 2>(ctx, a, s);
+        default: return launch_accum<1, 1>(ctx, a, s);
+    }
+}
+
+// The re-cut tail (csd_route.h: tail_split).  Splits > 0 leave partial sums in library scratch that a fixed-order
+// reduction adds afterwards (deterministic, no atomics).
+int launch_tail(spyhip_ctx* ctx, CsdArgs a, const CsdStep& s) {
+    const int nsplit = s.split.nsplit;
+    if (nsplit < 2) return launch_accum<1, 1>(ctx, a, s);
+    const int f0 = (int)(s.item0 / a.ntiles), nf = a.F - f0;
+    const size_t need = (size_t)(nsplit - 1) * nf * a.C * a.C * sizeof(float2);
     if (need > ctx->scratch_bytes) {
         if (ctx->scratch) { (void)hipFree(ctx->scratch); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
         SPY_HIP_CHECK(hipMalloc(&ctx->scratch, need));
         ctx->scratch_bytes = need;
     }
-    a.rows_per_split = ((nrows + nsplit - 1) / nsplit + 3) & ~3LL;
-    nsplit = (nrows + a.rows_per_split - 1) / a.rows_per_split;
+    a.rows_per_split = s.split.rows_per_split;
     a.part = reinterpret_cast<float2*>(ctx->scratch);
     a.part_f0 = f0;
     a.part_nf = nf;
-    int rc = launch_accum<1, 1>(ctx, a, first, a.nitems, (int)nsplit);
+    int rc = launch_accum<1, 1>(ctx, a, s);
     if (rc) return rc;
-    if (nsplit > 1) {
-        const long long n = (long long)nf * nchan * nchan;
-        hipLaunchKernelGGL(spycsd::csd_reduce_parts_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 4096)),
-                           dim3(256), 0, ctx->stream, a.acc, a.part, (int)nsplit - 1, f0, nf, nchan);
-        SPY_HIP_CHECK(hipGetLastError());
-    }
+    const long long n = (long long)nf * a.C * a.C;
+    hipLaunchKernelGGL(spycsd::csd_reduce_parts_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 4096)),
+                       dim3(256), 0, ctx->stream, a.acc, a.part, nsplit - 1, f0, nf, a.C);
+    SPY_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
@@ -101,21 +91,74 @@ __global__ void __launch_bounds__(256) csd_rank1_kernel(const float2* __restrict
     }
 }
 
-// packed rows to give the 3M kernel when the workgroups beyond the last full round of the chip go to the re-cut tail
-long long m3_main_rows(spyhip_ctx* ctx, long long nprow, int np) {
-    const long long nwg = nprow * np, rem = nwg % ctx->num_cu;
-    if (nwg > ctx->num_cu && rem > 0 && rem * 4 <= ctx->num_cu) return nprow - (rem + np - 1) / np;
-    return nprow;
+// Launch the steps of a route in order.  spec_d / acc_d: the spectra (row 0) and the accumulator of the update.
+int run_route(spyhip_ctx* ctx, const spycsd::CsdRoute& r, const void* spec_d, void* acc_d, int nfreq, int nchan, int blocked) {
+    if (r.err) { spy::set_error("%s", r.message.c_str()); return r.err; }
+    CsdArgs base{};
+    base.F = nfreq; base.C = nchan;
+    base.acc = reinterpret_cast<float2*>(acc_d);
+    base.nt = r.nt; base.ntiles = r.ntiles; base.nitems = r.nitems; base.cpad = r.cpad;
+    base.blocked = blocked;
+    base.fast_per = r.fast_per; base.fast_nwgf = r.fast_nwgf;
+    for (const CsdStep& s : r.steps) {
+        CsdArgs a = base;
+        a.spec = reinterpret_cast<const float2*>(spec_d) + (size_t)s.row0 * nfreq * nchan;
+        a.nrows = s.nrows;
+        a.item_base = s.item0; a.item_end = s.item1;
+        a.ctot = s.n0 ? nchan : 0;
+        a.ch0 = s.ch0; a.n0 = s.n0; a.ch1 = s.ch1; a.n1 = s.n1;
+        int rc = 0;
+        switch (s.kind) {
+            case StepKind::ACCUM: rc = launch_accum(ctx, a, s); break;
+            case StepKind::TAIL: rc = launch_tail(ctx, a, s); break;
+            case StepKind::M3_EXACT: rc = spycsd::m3_launch(256, ctx->stream, a, s.nprow); break;
+            case StepKind::M3_PADDED: rc = spycsd::m3_launch_padded(s.chp, ctx->stream, a, s.nprow); break;
+            case StepKind::M4_BLOCK: rc = spycsd::m4_launch_block(ctx->stream, a, s.nprow); break;
+            case StepKind::M3_RECT: rc = spycsd::m3_launch_rect(ctx->stream, a, s.nprow); break;
+            case StepKind::M4_RECT: rc = spycsd::m4_launch_rect(ctx->stream, a, s.nprow); break;
+            case StepKind::RANK1: {
+                const long long tot = (long long)nfreq * nchan * nchan;
+                hipLaunchKernelGGL(csd_rank1_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 65535)), dim3(256), 0,
+                                   ctx->stream, a.spec, nfreq, nchan, a.acc);
+                SPY_HIP_CHECK(hipGetLastError());
+                break;
+            }
+        }
+        if (rc == -100) { spy::set_error("csd_accumulate: no 3M kernel for %d channels", s.n0 ? s.n0 : nchan); return -1; }
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+spycsd::CsdQuery make_query(const spyhip_ctx* ctx, int64_t nrows, int nfreq, int nchan, int blocked) {
+    spycsd::CsdQuery q;
+    q.nchan = nchan; q.nfreq = nfreq; q.nrows = nrows;
+    q.blocked = blocked != 0;
+    q.phase_exact = ctx->csd_phase_exact != 0;
+    q.num_cu = ctx->num_cu;
+    q.lds_per_block = ctx->lds_per_block;
+    return q;                       // (have_m3 stays null: csd3m_{a..h}.hip + csd3m_x.hip hold every width up to 512)
+}
+
+int csd_accumulate_impl(spyhip_ctx* ctx, const void* spec_d, int64_t nrows, int nfreq, int nchan, void* acc_d, int blocked) {
+    if (!ctx || !spec_d || !acc_d) { spy::set_error("csd_accumulate: null argument"); return -1; }
+    if (nrows < 0 || nfreq < 1 || nchan < 1) { spy::set_error("csd_accumulate: bad shape"); return -1; }
+    if (nrows == 0) return 0;
+    SPY_HIP_CHECK(hipSetDevice(ctx->device));
+    return run_route(ctx, spycsd::csd_route(make_query(ctx, nrows, nfreq, nchan, blocked)), spec_d, acc_d, nfreq, nchan, blocked);
 }
 
 }  // namespace
 
-static int csd_accumulate_impl(spyhip_ctx* ctx, const void* spec_d, int64_t nrows, int nfreq, int nchan, void* acc_d,
-                               int blocked, bool only_4m = false);
-
 extern "C" int spyhip_csd_set_phase_exact(spyhip_ctx* ctx, int on) {
     if (!ctx) { spy::set_error("csd_set_phase_exact: null context"); return -1; }
     ctx->csd_phase_exact = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int spyhip_csd_kernel_name(spyhip_ctx* ctx, int nchan, int blocked, char* buf, int cap) {
+    if (!ctx || !buf || cap < 1 || nchan < 1) { spy::set_error("csd_kernel_name: null argument / bad shape"); return -1; }
+    std::snprintf(buf, (size_t)cap, "%s", spycsd::csd_kernel_name(make_query(ctx, 1, 1, nchan, blocked), !env_f32()).c_str());
     return 0;
 }
 
@@ -126,19 +169,18 @@ extern "C" int spyhip_csd_accumulate(spyhip_ctx* ctx, const void* spec_d, int64_
 }
 
 // K4h (csdh_kernel.h): 256 channels on the half-precision matrix cores with split float32 operands.  The frequencies
-// beyond the last full round of workgroups go to the re-cut float32 tail like on the other paths.  [f0, f0 + nf): the
-// frequencies of this call - a caller that wants the results of a range while the next is still being accumulated (the
-// coherence pipeline: normalisation and host copy of range r under the products of range r + 1) launches range by range.
+// beyond the last full round of workgroups go to the re-cut float32 tail like on the other paths (csd_route.h: csdh_route).
+// [f0, f0 + nf): the frequencies of this call - a caller that wants the results of a range while the next is still being
+// accumulated (the coherence pipeline: normalisation and host copy of range r under the products of range r + 1) launches
+// range by range.
 static int csd_accumulate_split_range(spyhip_ctx* ctx, const void* spec_d, int64_t nrows, int nfreq, int nchan, void* acc_d,
                                       const float* absmax_d, int f0, int nf) {
-    static const bool env_f32 = std::getenv("SPYHIP_CSD_F32") != nullptr;
     if (!spec_d || !acc_d || nfreq < 1 || f0 < 0 || nf < 0 || f0 + nf > nfreq) {
         spy::set_error("csd_accumulate_split: null argument / bad shape");
         return -1;
     }
     if (nf == 0) return 0;
     SPY_HIP_CHECK(hipSetDevice(ctx->device));
-    (void)env_f32;
     if (!ctx->k4h_done) SPY_HIP_CHECK(hipEventCreateWithFlags(&ctx->k4h_done, hipEventDisableTiming));
     else SPY_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->k4h_done, 0));      // the previous call's flag readers are through
     const size_t need = (size_t)nfreq * sizeof(int) + 256 * sizeof(float);
@@ -157,34 +199,21 @@ static int csd_accumulate_split_range(spyhip_ctx* ctx, const void* spec_d, int64
         if (rc) return rc;
         absmax_d = own_max;
     }
-    const long long rem = nfreq % ctx->num_cu;
-    int f_main = nfreq;
-    if (nfreq > ctx->num_cu && rem > 0 && rem * 4 <= ctx->num_cu) f_main = nfreq - (int)rem;
-    const int f1 = f0 + nf, h1 = std::min(f1, f_main);
-    if (f1 > f_main && f1 != nfreq) {          // the re-cut float32 tail [f_main, nfreq) goes in one piece
-        spy::set_error("csd_accumulate_split_range: a range beyond frequency %d must end at nfreq = %d", f_main, nfreq);
-        return -1;
-    }
+    const spycsd::CsdhRoute r = spycsd::csdh_route(make_query(ctx, nrows, nfreq, 256, 0), f0, nf);
+    if (r.err) { spy::set_error("%s", r.message.c_str()); return r.err; }
     int rc = 0;
-    if (h1 > f0)
-        rc = spycsd::csdh_run(ctx->stream, spec, nrows, nfreq, reinterpret_cast<float2*>(acc_d), absmax_d, flags, f0, h1 - f0,
+    if (r.h1 > r.h0)
+        rc = spycsd::csdh_run(ctx->stream, spec, nrows, nfreq, reinterpret_cast<float2*>(acc_d), absmax_d, flags, r.h0, r.h1 - r.h0,
                               ctx->csd_phase_exact != 0);
-    ctx->k4h_nf = f_main;
+    ctx->k4h_nf = r.f_main;
     if (!rc) SPY_HIP_CHECK(hipEventRecord(ctx->k4h_done, ctx->stream));         // (behind csdh_kernel and its only_flagged stand-in)
-    if (rc || f1 <= f_main) return rc;
-    CsdArgs a{};
-    a.spec = spec;
-    a.nrows = nrows; a.F = nfreq; a.C = 256;
-    a.acc = reinterpret_cast<float2*>(acc_d);
-    a.nt = 8; a.ntiles = 36; a.nitems = (long long)nfreq * 36; a.cpad = 256;
-    a.fast_per = 36;
-    return launch_tail(ctx, a, (long long)std::max(f0, f_main) * 36, nrows, nfreq, 256);
+    if (rc) return rc;
+    return run_route(ctx, r.tail, spec_d, acc_d, nfreq, 256, 0);
 }
 
 extern "C" int spyhip_csd_accumulate_split(spyhip_ctx* ctx, const void* spec_d, int64_t nrows, int nfreq, int nchan,
                                            void* acc_d, const float* absmax_d) {
-    static const bool env_f32 = std::getenv("SPYHIP_CSD_F32") != nullptr;
-    if (!ctx || nchan != 256 || nrows < 1 || env_f32) {
+    if (!ctx || nchan != 256 || nrows < 1 || env_f32()) {
         if (ctx) ctx->k4h_nf = 0;           // spyhip_csd_split_fallbacks reports THIS call: nothing went to the half-precision kernel
         return csd_accumulate_impl(ctx, spec_d, nrows, nfreq, nchan, acc_d, 0);
     }
@@ -193,8 +222,7 @@ extern "C" int spyhip_csd_accumulate_split(spyhip_ctx* ctx, const void* spec_d, 
 
 extern "C" int spyhip_csd_accumulate_split_range(spyhip_ctx* ctx, const void* spec_d, int64_t nrows, int nfreq, int nchan,
                                                  void* acc_d, const float* absmax_d, int f0, int nf) {
-    static const bool env_f32 = std::getenv("SPYHIP_CSD_F32") != nullptr;
-    if (!ctx || nchan != 256 || nrows < 1 || env_f32 || !absmax_d) {
+    if (!ctx || nchan != 256 || nrows < 1 || env_f32() || !absmax_d) {
         spy::set_error("csd_accumulate_split_range: 256 channels, at least one row and the range of the spectra (absmax_d) are required");
         return -1;
     }
@@ -219,145 +247,10 @@ extern "C" int spyhip_csd_accumulate_blocked(spyhip_ctx* ctx, const void* spec_d
     return csd_accumulate_impl(ctx, spec_d, nrows, nfreq, nchan, acc_d, 1);
 }
 
-static int csd_accumulate_impl(spyhip_ctx* ctx, const void* spec_d, int64_t nrows, int nfreq, int nchan, void* acc_d,
-                               int blocked, bool only_4m) {
-    if (!ctx || !spec_d || !acc_d) { spy::set_error("csd_accumulate: null argument"); return -1; }
-    if (nrows < 0 || nfreq < 1 || nchan < 1) { spy::set_error("csd_accumulate: bad shape"); return -1; }
-    if (nrows == 0) return 0;
-    SPY_HIP_CHECK(hipSetDevice(ctx->device));
-    CsdArgs a{};
-    a.spec = reinterpret_cast<const float2*>(spec_d);
-    a.nrows = nrows; a.F = nfreq; a.C = nchan;
-    a.acc = reinterpret_cast<float2*>(acc_d);
-    a.nt = (nchan + 31) / 32;
-    a.ntiles = a.nt * (a.nt + 1) / 2;
-    a.nitems = (long long)nfreq * a.ntiles;
-    a.cpad = a.nt * 32;
-    a.blocked = blocked;
-    // The instruction-lean path: C <= 256, row-major spectra.  A 256-element LDS row holds nfb consecutive
-    // frequencies (1 for C > 128, 2 for C = 128, 4 for C = 64, ...) and a workgroup owns their nfb * ntiles <= 40 tiles.
-    const bool fast = !blocked && nchan <= 256;            // (odd C: 8-byte staging loads instead of 16-byte ones)
-    if (fast) {
-        int nfb = 256 / nchan;
-        while (nfb > 1 && nfb * a.ntiles > 40) --nfb;
-        if (nfb > nfreq) nfb = nfreq;
-        a.fast_per = nfb * a.ntiles;
-    }
-    // C in (256, 512]: the same path with 512-element rows; the tiles of a frequency are shared by
-    // ceil(ntiles / 40) workgroups (512 channels: 4 x 34 tiles), each staging the whole row.
-    // spyhip_csd_set_phase_exact selects them per context (imag / angle outputs, see include/spyhip.h).
-    const bool force_4m = ctx->csd_phase_exact != 0 || only_4m;
-    const bool wide3m = !force_4m && nchan > 256 && spycsd::m3_available(nchan);
-    if (!blocked && nchan > 256 && nchan <= 512 && !wide3m) {
-        a.fast_nwgf = (a.ntiles + 39) / 40;
-        a.fast_per = (a.ntiles + a.fast_nwgf - 1) / a.fast_nwgf;
-        const long long nwg = (long long)nfreq * a.fast_nwgf;
-        long long f_main = nfreq;
-        const long long rem = nwg % ctx->num_cu;
-        if (nwg > ctx->num_cu && rem > 0 && rem * 4 <= ctx->num_cu) f_main = ((nwg - rem) / a.fast_nwgf);
-        int rc = launch_accum<5, 4, 3>(ctx, a, 0, f_main * a.ntiles);
-        if (rc || f_main == nfreq) return rc;
-        return launch_accum<1, 1>(ctx, a, f_main * a.ntiles, a.nitems);     // the last partial round, re-cut
-    }
-    // 256 channels, row-major spectra: the 3-multiplication kernel, one workgroup per frequency; the workgroups
-    // beyond the last full round (F = 2049 on 256 CUs: one frequency) go to the re-cut tail like on the other paths.
-    if (nchan == 256 && !force_4m) {         // either hand-over layout: the kernel's LDS copies gather
-        const long long nwg = nfreq, rem = nwg % ctx->num_cu;
-        long long f_main = nfreq;
-        if (nwg > ctx->num_cu && rem > 0 && rem * 4 <= ctx->num_cu) f_main = nwg - rem;
-        int rc = spycsd::m3_launch(256, ctx->stream, a, f_main);
-        if (rc == -100) { spy::set_error("csd_accumulate: no 3M kernel for 256 channels"); return -1; }
-        if (rc || f_main == nfreq) return rc;
-        return launch_tail(ctx, a, f_main * a.ntiles, nrows, nfreq, nchan);
-    }
-    // every other channel count up to 512, row-major spectra: the 3M kernel instance of the next multiple of 16 with
-    // the narrower rows padded inside its LDS image (csd3m_kernel.h, EXACT = false).  Below 256 (padded) channels
-    // floor(256 / CHp) frequencies per workgroup (the last packed row may be partial); above, 512-element LDS rows and
-    // several workgroups per frequency.  Odd channel counts: the last row of spectra goes to the 4-multiplication
-    // kernels (the 16-byte copy of the last channel reaches 8 bytes beyond its frequency).
-    if (nchan != 256 && !blocked && !force_4m && spycsd::m3_available(nchan)) {
-        const int chp = spycsd::m3_padded(nchan);
-        const int64_t nrows3 = (nchan & 1) ? nrows - 1 : nrows;
-        if (nrows3 > 0) {
-            CsdArgs b = a;
-            b.nrows = nrows3;
-            const int fpr = chp < 256 ? 256 / chp : 1;
-            const long long nprow = (nfreq + fpr - 1) / fpr;
-            const long long p_main = m3_main_rows(ctx, nprow, spycsd::m3_parts(nchan));
-            int rc = spycsd::m3_launch(nchan, ctx->stream, b, p_main);
-            if (rc == -100) { spy::set_error("csd_accumulate: no 3M kernel for %d channels", nchan); return -1; }
-            if (rc) return rc;
-            if (p_main < nprow && (rc = launch_tail(ctx, b, fpr * p_main * a.ntiles, nrows3, nfreq, nchan))) return rc;
-        }
-        if (nrows3 == nrows) return 0;
-        return csd_accumulate_impl(ctx, reinterpret_cast<const float2*>(spec_d) + (size_t)nrows3 * nfreq * nchan, 1, nfreq, nchan,
-                                   acc_d, 0, true);
-    }
-    // more than 512 channels, row-major spectra: the lower triangle in blocks of 256 channels - the Hermitian product of
-    // every block with itself (the 3M instance of its width, reading its channel range out of the wide rows) and the
-    // rectangle of every pair of blocks (csd3m_kernel<512, 8, false, true>: the two ranges side by side in one
-    // 512-element LDS image, the 256 sub-tiles of the off-diagonal quadrant shared by three workgroups per frequency).
-    // No channel count is too wide for LDS any more: a launch never stages more than 512 channels.  Phase-exact
-    // accumulation (force_4m) takes the same walk with the 4-multiplication instances of the tiled kernel (the 32 x 32-tile
-    // kernels below cannot stage rows this wide).
-    if (nchan > 512 && !blocked) {
-        const int64_t nrows3 = (nchan & 1) ? nrows - 1 : nrows;
-        const int nb = (nchan + 255) / 256;
-        if (nrows3 > 0) {
-            CsdArgs b = a;
-            b.nrows = nrows3;
-            b.ctot = nchan;
-            for (int I = 0; I < nb; ++I) {
-                const int nI = std::min(256, nchan - 256 * I);
-                b.ch0 = 256 * I; b.n0 = nI; b.ch1 = 0; b.n1 = 0;
-                const int chp = force_4m ? 256 : spycsd::m3_padded(nI);
-                const int fpr = chp < 256 ? 256 / chp : 1;
-                int rc = force_4m ? spycsd::m4_launch_block(ctx->stream, b, nfreq)
-                                  : spycsd::m3_launch_padded(chp, ctx->stream, b, (nfreq + fpr - 1) / fpr);
-                if (rc == -100) { spy::set_error("csd_accumulate: no 3M kernel for a block of %d channels", nI); return -1; }
-                if (rc) return rc;
-                for (int J = 0; J < I; ++J) {
-                    b.ch0 = 256 * J; b.n0 = 256; b.ch1 = 256 * I; b.n1 = nI;
-                    if ((rc = force_4m ? spycsd::m4_launch_rect(ctx->stream, b, nfreq) : spycsd::m3_launch_rect(ctx->stream, b, nfreq)))
-                        return rc;
-                }
-            }
-        }
-        if (nrows3 < nrows) {
-            const long long tot = (long long)nfreq * nchan * nchan;
-            hipLaunchKernelGGL(csd_rank1_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 65535)), dim3(256), 0,
-                               ctx->stream, reinterpret_cast<const float2*>(spec_d) + (size_t)nrows3 * nfreq * nchan, nfreq, nchan,
-                               reinterpret_cast<float2*>(acc_d));
-            SPY_HIP_CHECK(hipGetLastError());
-        }
-        return 0;
-    }
-    // tiles per wave (waves 0-3, waves 4-7): (5,4) packs the 36 tiles of C=256 into one workgroup per frequency
-    if (fast || a.ntiles >= 21) {
-        // One workgroup per CU: F = 2049 frequencies on 256 CUs would leave a 9th, almost empty round.
-        // The workgroups beyond the last full round are re-cut into 1-tile-per-wave workgroups
-        // (4.5x more, each 5x shorter), so the tail costs ~1/5 of a round and stays deterministic.
-        const long long per = fast ? a.fast_per : 36, nwg = (a.nitems + per - 1) / per;
-        const long long full = (nwg / ctx->num_cu) * ctx->num_cu, rem = nwg - full;
-        if (full > 0 && rem > 0 && rem * 4 <= ctx->num_cu) {
-            // 36 tiles in every workgroup (C = 256): the variant without per-tile guards
-            int rc = !fast ? launch_accum<5, 4>(ctx, a, 0, full * per)
-                           : (nchan == 256 ? launch_accum<5, 4, 1>(ctx, a, 0, full * per)
-                                             : launch_accum<5, 4, 2>(ctx, a, 0, full * per));
-            if (rc) return rc;
-            return launch_tail(ctx, a, full * per, nrows, nfreq, nchan);
-        }
-        if (!fast) return launch_accum<5, 4>(ctx, a, 0, a.nitems);
-        return nchan == 256 ? launch_accum<5, 4, 1>(ctx, a, 0, a.nitems) : launch_accum<5, 4, 2>(ctx, a, 0, a.nitems);
-    }
-    if (a.ntiles >= 6) return launch_accum<3, 2>(ctx, a, 0, a.nitems);
-    return launch_accum<1, 1>(ctx, a, 0, a.nitems);
-}
-
 extern "C" int spyhip_csd_finalize(spyhip_ctx* ctx, void* acc_d, int nfreq, int nchan, double scale) {
     if (!ctx || !acc_d) { spy::set_error("csd_finalize: null argument"); return -1; }
     SPY_HIP_CHECK(hipSetDevice(ctx->device));
-    const long long nt = (nchan + 31) / 32, blocks = (long long)nfreq * (nt * (nt + 1) / 2);
+    const long long blocks = (long long)nfreq * spycsd::tri_tiles(nchan);
     if (blocks > 0x7fffffffLL) { spy::set_error("csd_finalize: grid too large"); return -1; }
     hipLaunchKernelGGL(spycsd::csd_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
                        reinterpret_cast<float2*>(acc_d), nfreq, nchan, (float)scale);
@@ -370,7 +263,7 @@ extern "C" int spyhip_coh_from_accumulator(spyhip_ctx* ctx, const void* acc_d, i
     if (!ctx || !acc_d || !out_d) { spy::set_error("coh_from_accumulator: null argument"); return -1; }
     if (output < SPYHIP_OUT_POW || output > SPYHIP_OUT_ABSIMAG) { spy::set_error("coh_from_accumulator: bad output %d", output); return -1; }
     SPY_HIP_CHECK(hipSetDevice(ctx->device));
-    const long long nt = (nchan + 31) / 32, blocks = (long long)nfreq * (nt * (nt + 1) / 2);
+    const long long blocks = (long long)nfreq * spycsd::tri_tiles(nchan);
     if (blocks > 0x7fffffffLL) { spy::set_error("coh_from_accumulator: grid too large"); return -1; }
     if (output == SPYHIP_OUT_FOURIER)
         hipLaunchKernelGGL(spycsd::coh_from_acc_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
@@ -442,7 +335,7 @@ extern "C" int spyhip_jack_coh_accumulate(spyhip_ctx* ctx, const void* spec_d, i
     a.T = (float)ntrials_total;
     a.sum_d = reinterpret_cast<double*>(sum_d);
     a.sum_d2 = reinterpret_cast<double*>(sum_d2);
-    const long long nt = (nchan + 31) / 32, blocks = 8LL * ((nfreq + 7) / 8) * (nt * (nt + 1) / 2);
+    const long long blocks = 8LL * ((nfreq + 7) / 8) * spycsd::tri_tiles(nchan);
     if (blocks > 0x7fffffffLL) { spy::set_error("jack_coh_accumulate: grid too large"); return -1; }
     const size_t lds = 2 * (size_t)2 * ntaper * 32 * sizeof(float2);
     if (lds > ctx->lds_per_block) { spy::set_error("jack_coh_accumulate: %d tapers do not fit the LDS staging buffer", ntaper); return -3; }

@@ -1,5 +1,6 @@
 // Dispatcher over the translation units of the 3-multiplication kernels (csd3m_launch.h)
 #include "csd3m_launch.h"
+#include "csd_route.h"
 
 namespace spycsd {
 int m3_launch_exact256(hipStream_t stream, CsdArgs a, long long nprow);
@@ -29,6 +30,4 @@ int m3_launch_padded(int chp, hipStream_t stream, CsdArgs a, long long nprow) {
     if ((rc = m3_launch_h(chp, stream, a, nprow)) != -100) return rc;
     return -100;
 }
-
-bool m3_available(int nchan) { return nchan >= 1 && nchan <= 512; }
 }  // namespace spycsd

@@ -357,10 +357,17 @@ def set_blocked(on):
     lib().emu_set_blocked(C.c_int(int(bool(on))))
 
 
-def csd_accumulate(spec, acc, force_tpw=0, blocked=False, force_4m=False):
+def csd_accumulate(spec, acc, force_tpw=0, blocked=False, force_4m=False, num_cu=None):
     """Emulated spyhip_csd_accumulate: spec (R, F, C) complex64 - or (R, ceil(C/4), F, 4) with blocked=True -,
     acc (F, C, C) complex64 (in place).  `force_4m`: 256 channels on the 4-multiplication kernel (SPYHIP_CSD_4M).
+    `num_cu`: compute units the route plans for (emulator only; None: so many that no launch is re-cut into a tail).
     Returns a code for the kernel that ran (8 = the 3-multiplication kernel)."""
+    if num_cu is not None:
+        lib().emu_set_num_cu(C.c_longlong(num_cu))
+        try:
+            return csd_accumulate(spec, acc, force_tpw, blocked, force_4m)
+        finally:
+            lib().emu_set_num_cu(C.c_longlong(0))
     if force_4m:
         lib().emu_set_force_4m(1)
         try:

@@ -15,6 +15,8 @@ thread_local BlockCtx* t_ctx = nullptr;
 #include "../../include/spyhip.h"
 #include "../../syncopy_amd/csrc/mtmfft_kernel.h"
 #include "../../syncopy_amd/csrc/mtmfft_generic.h"
+#include "../../syncopy_amd/csrc/csd_route.h"
+#include "emu_m3_widths.h"
 #include "../../syncopy_amd/csrc/csd_kernel.h"
 #include "../../syncopy_amd/csrc/csd3m_kernel.h"
 #include "../../syncopy_amd/csrc/ppc_kernel.h"
@@ -119,6 +121,7 @@ static void run_dec_mode(const MtmArgs& a0, int nseg, int nchan, int outk, int m
 
 static int g_blocked = 0;   // hand-over layout toggle shared by the FFT and CSD entry points
 static int g_force_4m = 0;  // SPYHIP_CSD_4M: 256 channels on the 4-multiplication kernel
+static long long g_num_cu = 1LL << 40;  // compute units the CSD route plans for; the default is so many that nothing is re-cut
 static const float* g_means = nullptr;   // (nseg x nchan) reference-order means for the next FFT call, or none
 static const float* g_twh = nullptr;     // exp(-2 pi i f / nfft), f <= nfft / 4: the table of the HALF-form schedules
 
@@ -161,6 +164,7 @@ extern "C" {
 
 void emu_set_blocked(int on) { g_blocked = on; }
 void emu_set_force_4m(int on) { g_force_4m = on; }
+void emu_set_num_cu(long long n) { g_num_cu = n > 0 ? n : 1LL << 40; }
 void emu_set_means(const float* m) { g_means = m; }
 void emu_set_twh(const float* t) { g_twh = t; }
 
@@ -492,159 +496,138 @@ int emu_mtmfft_mixed(int nfft, int force_nostage, int* info, const float* data, 
     return 0;
 }
 
-// Mirrors spyhip_csd_accumulate (host logic of csd.hip) for the emulated MFMA kernel.
+// spyhip_csd_accumulate for the emulated kernels: the route of csd_route.h (the one csd.hip launches), asked with the
+// emulator's sample of 3M instances and walked with emu::launch.  force_tpw (1, 3, 5) is the test-only override that picks
+// a generic csd_accum_kernel<TA, TB> directly.  Returns a code for the first kernel: 1 / 3 / 5 generic tiles per wave,
+// 6 the instruction-lean path, 7 its wide variant, 8 / 9 the 3M kernel (exact 256 / padded), 10 / 11 the 256-channel
+// block walk (3M / 4M).
+}  // extern "C"
+
+template <int TA, int TB, int FAST = 0>
+static void emu_accum(spycsd::CsdArgs a, const spycsd::AccumGeometry& g, int nsplit = 1) {
+    a.kb = g.kb;
+    if (g.grid > 0)
+        emu::launch(dim3((unsigned)g.grid, (unsigned)nsplit), dim3(spycsd::CSD_THREADS), g.lds,
+                    [&] { spycsd::csd_accum_kernel<TA, TB, FAST>(a); });
+}
+
+static void emu_accum(const spycsd::CsdArgs& a, int ta, int fast, const spycsd::AccumGeometry& g) {
+    switch (ta * 10 + fast) {
+        case 50: emu_accum<5, 4>(a, g); break;
+        case 51: emu_accum<5, 4, 1>(a, g); break;
+        case 52: emu_accum<5, 4, 2>(a, g); break;
+        case 53: emu_accum<5, 4, 3>(a, g); break;
+        case 30: emu_accum<3, 2>(a, g); break;
+        default: emu_accum<1, 1>(a, g); break;
+    }
+}
+
+// grid of m3_launch_one (csd3m_launch_impl.h)
+template <int CH, bool EXACT, bool RECT = false, bool M4 = false>
+static void emu_m3(spycsd::CsdArgs a, long long nprow) {
+    constexpr int NP = spycsd::M3Tab<CH, RECT>::NP;
+    a.item_base = 0;
+    a.item_end = nprow * spycsd::M3_TILES_PER_F;
+    const long long grid = NP > 1 ? ((nprow + 7) / 8) * 8 * NP : (a.blocked ? ((nprow + 31) / 32) * 32 : nprow);
+    if (nprow > 0)
+        emu::launch(dim3((unsigned)grid), dim3(512), spycsd::M3_LDS_BYTES, [&] { spycsd::csd3m_kernel<CH, 8, EXACT, RECT, M4>(a); });
+}
+
+extern "C" {
+
 int emu_csd_accumulate(const float* spec, long long nrows, int F, int C, float* acc, int force_tpw) {
-    spycsd::CsdArgs a{};
-    a.spec = reinterpret_cast<const float2*>(spec);
-    a.nrows = nrows; a.F = F; a.C = C;
-    a.acc = reinterpret_cast<float2*>(acc);
-    a.nt = (C + 31) / 32;
-    a.ntiles = a.nt * (a.nt + 1) / 2;
-    a.nitems = (long long)F * a.ntiles;
-    a.cpad = a.nt * 32;
-    a.blocked = g_blocked;
-    // as csd.hip: even C <= 256, row-major spectra -> the instruction-lean path (force_tpw != 0 picks a generic kernel)
-    const bool fast = force_tpw == 0 && !g_blocked && C <= 256;
-    int ta = 1, tb = 1;
-    if (fast || a.ntiles >= 21) { ta = 5; tb = 4; }
-    else if (a.ntiles >= 6) { ta = 3; tb = 2; }
-    if (force_tpw == 1) { ta = 1; tb = 1; }
-    if (force_tpw == 3) { ta = 3; tb = 2; }
-    if (force_tpw == 5) { ta = 5; tb = 4; }
-    int per = 4 * (ta + tb);
-    int nfb = (per + a.ntiles - 1) / a.ntiles;
-    if (per % a.ntiles != 0 && a.ntiles > 1) nfb += 1;
-    if (nfb > F) nfb = F;
-    const size_t rowbytes = (size_t)nfb * a.cpad * sizeof(float2);
-    int kb = 32;
-    while (kb > 4 && (size_t)kb * rowbytes > (size_t)spycsd::CSD_THREADS * spycsd::CSD_PF * sizeof(float2)) kb -= 4;
-    if (kb > nrows && !fast) kb = (int)((nrows + 3) & ~3LL);
-    size_t lds = 3 * (size_t)kb * rowbytes;
-    if (fast) {
-        int nf = 256 / C;
-        while (nf > 1 && nf * a.ntiles > 40) --nf;
-        if (nf > F) nf = F;
-        a.fast_per = nf * a.ntiles;
-        per = a.fast_per;
-        kb = 16;
-        lds = 3 * (size_t)16 * 256 * sizeof(float2) + 512;
+    using spycsd::StepKind;
+    spycsd::CsdQuery q;
+    q.nchan = C; q.nfreq = F; q.nrows = nrows;
+    q.blocked = g_blocked != 0;
+    q.phase_exact = g_force_4m != 0;
+    q.num_cu = g_num_cu;
+    q.have_m3 = emu_have_m3;
+    spycsd::CsdArgs base{};
+    base.F = F; base.C = C;
+    base.acc = reinterpret_cast<float2*>(acc);
+    base.blocked = g_blocked;
+    if (force_tpw) {                             // (asks no route: a shape the route refuses still reaches the generic kernel)
+        const int ta = force_tpw, tb = force_tpw == 1 ? 1 : force_tpw - 1;
+        if (ta != 1 && ta != 3 && ta != 5) return -1;
+        if (nrows < 0 || F < 1 || C < 1) return -1;
+        base.nt = (C + 31) / 32; base.ntiles = (int)spycsd::tri_tiles(C); base.cpad = base.nt * 32;
+        base.nitems = (long long)F * base.ntiles;
+        base.spec = reinterpret_cast<const float2*>(spec);
+        base.nrows = nrows;
+        base.item_end = base.nitems;
+        const spycsd::AccumGeometry g = spycsd::accum_geometry(ta, tb, 0, base.ntiles, base.cpad, F, nrows, 0, 0, q.lds_per_block, base.nitems);
+        if (g.err) return g.err;
+        if (nrows > 0) emu_accum(base, ta, 0, g);
+        return ta;
     }
-    a.kb = kb;
-    a.item_base = 0; a.item_end = a.nitems;
-    unsigned grid = (unsigned)((a.nitems + per - 1) / per);
-    const unsigned T = spycsd::CSD_THREADS;
-    const int chp_w = (C + 15) & ~15;
-    const bool wide3m = !g_force_4m && (chp_w == 304 || chp_w == 320 || chp_w == 384);   // (csd.hip: every count up to 512)
-    if (force_tpw == 0 && !g_blocked && C > 256 && C <= 512 && !wide3m) {      // as csd.hip: the wide variant
-        a.fast_nwgf = (a.ntiles + 39) / 40;
-        a.fast_per = (a.ntiles + a.fast_nwgf - 1) / a.fast_nwgf;
-        a.kb = 8;
-        grid = (unsigned)(F * a.fast_nwgf);
-        emu::launch(dim3(grid), dim3(T), 3 * (size_t)16 * 256 * sizeof(float2) + 512,
-                    [&] { spycsd::csd_accum_kernel<5, 4, 3>(a); });
-        return 7;
-    }
-    if (force_tpw == 0 && C == 256 && !g_force_4m) {
-        // as csd.hip: 256 channels take the 3-multiplication kernel, one workgroup of 8 waves per frequency
-        a.item_end = (long long)F * spycsd::M3_TILES_PER_F;
-        emu::launch(dim3((unsigned)F), dim3(512), spycsd::M3_LDS_BYTES, [&] { spycsd::csd3m_kernel<256, 8>(a); });
-        return 8;
-    }
-    if (force_tpw == 0 && C > 512 && !g_blocked) {
-        // as csd.hip: blocks of 256 channels - Hermitian product per block (instances 16 / 256 here), rectangle per pair
-        const long long nrows3 = (C & 1) ? nrows - 1 : nrows;
-        const int nb = (C + 255) / 256;
-        spycsd::CsdArgs b = a;
-        b.nrows = nrows3;
-        b.ctot = C;
-        for (int I = 0; I < nb && nrows3 > 0; ++I) {
-            const int nI = std::min(256, C - 256 * I);
-            b.ch0 = 256 * I; b.n0 = nI; b.ch1 = 0; b.n1 = 0;
-            const int chp = g_force_4m ? 256 : (nI + 15) & ~15, fpr = chp < 256 ? 256 / chp : 1;
-            const long long nprow = (F + fpr - 1) / fpr;
-            b.item_base = 0; b.item_end = nprow * spycsd::M3_TILES_PER_F;
-            if (g_force_4m) emu::launch(dim3((unsigned)nprow), dim3(512), spycsd::M3_LDS_BYTES, [&] { spycsd::csd3m_kernel<256, 8, false, false, true>(b); });
-            else if (chp == 256) emu::launch(dim3((unsigned)nprow), dim3(512), spycsd::M3_LDS_BYTES, [&] { spycsd::csd3m_kernel<256, 8, false>(b); });
-            else if (chp == 16) emu::launch(dim3((unsigned)nprow), dim3(512), spycsd::M3_LDS_BYTES, [&] { spycsd::csd3m_kernel<16, 8, false>(b); });
-            else return -1;
-            for (int J = 0; J < I; ++J) {
-                b.ch0 = 256 * J; b.n0 = 256; b.ch1 = 256 * I; b.n1 = nI;
-                b.item_base = 0; b.item_end = (long long)F * spycsd::M3_TILES_PER_F;
-                constexpr int NPR = spycsd::M3Tab<512, true>::NP;
-                if (g_force_4m)
-                    emu::launch(dim3((unsigned)(((F + 7) / 8) * 8 * NPR)), dim3(512), spycsd::M3_LDS_BYTES,
-                                [&] { spycsd::csd3m_kernel<512, 8, false, true, true>(b); });
-                else
-                    emu::launch(dim3((unsigned)(((F + 7) / 8) * 8 * NPR)), dim3(512), spycsd::M3_LDS_BYTES,
-                                [&] { spycsd::csd3m_kernel<512, 8, false, true>(b); });
+    const spycsd::CsdRoute r = spycsd::csd_route(q);
+    if (r.err) return r.err;
+    base.nt = r.nt; base.ntiles = r.ntiles; base.nitems = r.nitems; base.cpad = r.cpad;
+    base.fast_per = r.fast_per; base.fast_nwgf = r.fast_nwgf;
+    for (const spycsd::CsdStep& s : r.steps) {
+        spycsd::CsdArgs a = base;
+        a.spec = reinterpret_cast<const float2*>(spec) + (size_t)s.row0 * F * C;
+        a.nrows = s.nrows;
+        a.item_base = s.item0; a.item_end = s.item1;
+        a.ctot = s.n0 ? C : 0;
+        a.ch0 = s.ch0; a.n0 = s.n0; a.ch1 = s.ch1; a.n1 = s.n1;
+        switch (s.kind) {
+            case StepKind::ACCUM: emu_accum(a, s.ta, s.fast, s.geo); break;
+            case StepKind::TAIL: {               // launch_tail of csd.hip with the scratch on the host
+                const int f0 = (int)(s.item0 / r.ntiles), nf = F - f0, nsplit = s.split.nsplit;
+                const long long n = (long long)nf * C * C;
+                std::vector<float2> part(nsplit > 1 ? (size_t)(nsplit - 1) * n : 0);
+                if (nsplit > 1) { a.rows_per_split = s.split.rows_per_split; a.part = part.data(); a.part_f0 = f0; a.part_nf = nf; }
+                emu_accum<1, 1>(a, s.geo, nsplit);
+                if (nsplit > 1)
+                    emu::launch(dim3((unsigned)std::min<long long>((n + 255) / 256, 4096)), dim3(256), 0,
+                                [&] { spycsd::csd_reduce_parts_kernel(a.acc, a.part, nsplit - 1, f0, nf, C); });
+                break;
             }
-        }
-        if (nrows3 < nrows) {                    // csd_rank1_kernel of csd.hip, on the host
-            const float2* x = a.spec + (size_t)nrows3 * F * C;
-            for (int f = 0; f < F; ++f)
-                for (int i = 0; i < C; ++i)
-                    for (int j = 0; j <= i; ++j) {
-                        const float2 u = x[(size_t)f * C + i], v = x[(size_t)f * C + j];
-                        float2& o = a.acc[((size_t)f * C + i) * C + j];
-                        o.x += u.x * v.x + u.y * v.y;
-                        o.y += u.y * v.x - u.x * v.y;
-                    }
-        }
-        return g_force_4m ? 11 : 10;
-    }
-    // (the emulator instantiates a sample of the 3M channel counts; the others take the 4-multiplication kernels here)
-    const int chp_emu = (C + 15) & ~15;
-    const bool have3m = chp_emu == 16 || chp_emu == 32 || chp_emu == 48 || chp_emu == 64 || chp_emu == 96 || chp_emu == 128 ||
-                        chp_emu == 192 || chp_emu == 240 || chp_emu == 256 || chp_emu == 304 || chp_emu == 320 || chp_emu == 384;
-    if (force_tpw == 0 && C != 256 && C <= 512 && !g_blocked && !g_force_4m && have3m) {
-        // as csd.hip: the 3-multiplication kernel instance of the next multiple of 16 with narrower rows padded inside
-        // its LDS image; floor(256 / CHp) frequencies per workgroup, or (above 256 channels) NP workgroups per
-        // frequency in XCD-aware order; odd channel counts: the last row through the 4-multiplication kernels
-        const int chp = (C + 15) & ~15;
-        const int fpr = chp < 256 ? 256 / chp : 1;
-        const long long nprow = (F + fpr - 1) / fpr;
-        const long long nrows3 = (C & 1) ? nrows - 1 : nrows;
-        a.item_end = nprow * spycsd::M3_TILES_PER_F;
-        a.nrows = nrows3;
-        const dim3 b(512);
-#define EMU_M3(CH)                                                                                                      \
-    case CH: {                                                                                                          \
-        const int np = spycsd::M3Tab<CH>::NP;                                                                           \
-        const dim3 g((unsigned)(np == 1 ? nprow : ((nprow + 7) / 8) * 8 * np));                                          \
-        if (nrows3 > 0) emu::launch(g, b, spycsd::M3_LDS_BYTES, [&] { spycsd::csd3m_kernel<CH, 8, false>(a); });          \
-        break;                                                                                                          \
-    }
-        switch (chp) {
-            EMU_M3(16) EMU_M3(32) EMU_M3(48) EMU_M3(64) EMU_M3(96) EMU_M3(128) EMU_M3(192) EMU_M3(240) EMU_M3(256) EMU_M3(304) EMU_M3(320) EMU_M3(384)
-            default: return -1;            // (the emulator instantiates a sample of the channel counts)
-        }
+            case StepKind::M3_EXACT: emu_m3<256, true>(a, s.nprow); break;
+            case StepKind::M3_PADDED:
+                switch (s.chp) {
+#define EMU_M3(CH) case CH: emu_m3<CH, false>(a, s.nprow); break;
+                    EMU_M3_WIDTHS(EMU_M3)
 #undef EMU_M3
-        if (nrows3 < nrows) {
-            const int keep = g_force_4m;
-            g_force_4m = 1;
-            emu_csd_accumulate(spec + (size_t)nrows3 * F * C * 2, 1, F, C, acc, 0);
-            g_force_4m = keep;
+                    default: return -1;            // (the route asked emu_have_m3, which reads the same list)
+                }
+                break;
+            case StepKind::M4_BLOCK: emu_m3<256, false, false, true>(a, s.nprow); break;
+            case StepKind::M3_RECT: emu_m3<512, false, true>(a, s.nprow); break;
+            case StepKind::M4_RECT: emu_m3<512, false, true, true>(a, s.nprow); break;
+            case StepKind::RANK1:                // csd_rank1_kernel of csd.hip, on the host
+                for (int f = 0; f < F; ++f)
+                    for (int i = 0; i < C; ++i)
+                        for (int j = 0; j <= i; ++j) {
+                            const float2 u = a.spec[(size_t)f * C + i], v = a.spec[(size_t)f * C + j];
+                            float2& o = a.acc[((size_t)f * C + i) * C + j];
+                            o.x += u.x * v.x + u.y * v.y;
+                            o.y += u.y * v.x - u.x * v.y;
+                        }
+                break;
         }
-        return 9;
     }
-    if (fast && C == 256) emu::launch(dim3(grid), dim3(T), lds, [&] { spycsd::csd_accum_kernel<5, 4, 1>(a); });
-    else if (fast) emu::launch(dim3(grid), dim3(T), lds, [&] { spycsd::csd_accum_kernel<5, 4, 2>(a); });
-    else if (ta == 5) emu::launch(dim3(grid), dim3(T), lds, [&] { spycsd::csd_accum_kernel<5, 4>(a); });
-    else if (ta == 3) emu::launch(dim3(grid), dim3(T), lds, [&] { spycsd::csd_accum_kernel<3, 2>(a); });
-    else emu::launch(dim3(grid), dim3(T), lds, [&] { spycsd::csd_accum_kernel<1, 1>(a); });
-    if (fast) return 6;
-    return ta;
+    if (r.steps.empty()) return 0;
+    const spycsd::CsdStep& s0 = r.steps.front();
+    switch (s0.kind) {
+        case StepKind::ACCUM: return s0.fast == 3 ? 7 : s0.fast ? 6 : s0.ta;
+        case StepKind::M3_EXACT: return 8;
+        case StepKind::M3_PADDED: return s0.n0 ? 10 : 9;
+        case StepKind::M4_BLOCK: return 11;
+        case StepKind::RANK1: return g_force_4m ? 11 : 10;
+        default: return -1;
+    }
 }
 
 void emu_csd_finalize(float* acc, int F, int C, float scale) {
-    const int nt = (C + 31) / 32;
-    emu::launch(dim3((unsigned)(F * (nt * (nt + 1) / 2))), dim3(256), 0,
+    emu::launch(dim3((unsigned)(F * spycsd::tri_tiles(C))), dim3(256), 0,
                 [&] { spycsd::csd_finalize_kernel(reinterpret_cast<float2*>(acc), F, C, scale); });
 }
 
 void emu_coh_from_accumulator(const float* acc, int F, int C, float scale, int kind, void* out) {
-    const int nt = (C + 31) / 32;
-    const dim3 grid((unsigned)(F * (nt * (nt + 1) / 2)));
+    const dim3 grid((unsigned)(F * spycsd::tri_tiles(C)));
     if (kind == SPYHIP_OUT_FOURIER)
         emu::launch(grid, dim3(256), 0, [&] { spycsd::coh_from_acc_kernel<true>(reinterpret_cast<const float2*>(acc), F, C, scale, kind, out); });
     else

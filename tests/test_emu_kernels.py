@@ -231,6 +231,28 @@ def test_csd_3m_kernel(C, F, R):
     assert_parity(acc, (ref / R).astype(np.complex64), what="3M csd finalised")
 
 
+@pytest.mark.parametrize("C,F,R,force_4m,code", [
+    # a chip of 4 compute units: 5 packed rows (3M) / 5 workgroups (4M) leave one beyond the full round, which is re-cut.
+    # 12 rows: fewer than the 128 a row split needs - the tail adds straight into the accumulator
+    (64, 17, 12, False, 9), (64, 17, 12, True, 6),
+    # 130 rows: the tail's rows go to 3 splits of 44, partial sums + csd_reduce_parts_kernel
+    (32, 33, 130, False, 9), (32, 33, 130, True, 6)])
+def test_csd_recut_tail(C, F, R, force_4m, code):
+    """The workgroups beyond the last full round of the chip, re-cut into 1-tile-per-wave workgroups (csd_route.h:
+    recut_main, tail_split; the steps tests/test_csd_route.py lists for these shapes), without and with the row split."""
+    rng = np.random.default_rng(C + R)
+    spec = (rng.normal(size=(R, F, C)) + 1j * rng.normal(size=(R, F, C))).astype(np.complex64)
+    acc = np.zeros((F, C, C), np.complex64)
+    assert E.csd_accumulate(spec, acc, force_4m=force_4m, num_cu=4) == code
+    whole = np.zeros((F, C, C), np.complex64)
+    E.csd_accumulate(spec, whole, force_4m=force_4m)              # no tail: the last frequencies in the main launch
+    ref = np.einsum("rfi,rfj->fij", spec.astype(np.complex128), spec.conj().astype(np.complex128))
+    ii, jj = np.tril_indices(C)
+    assert_parity(acc[:, ii, jj], ref[:, ii, jj].astype(np.complex64), what="csd with a re-cut tail, lower triangle")
+    assert_parity(whole[:, ii, jj], ref[:, ii, jj].astype(np.complex64), what="csd in one launch, lower triangle")
+    np.testing.assert_array_equal(acc[:-1], whole[:-1])          # the frequencies of the main launch: the same kernel
+
+
 @pytest.mark.parametrize("C,F,T,K", [(5, 4, 6, 3), (40, 2, 7, 1), (70, 1, 5, 7)])
 def test_ppc_kernel(C, F, T, K):
     """K7's kernel source on the CPU: phasor sums + closed form = the oracle's walk over all trial pairs."""
