@@ -15,8 +15,11 @@
 #pragma once
 #include "mtmfft_kernel.h"
 #include "fft2_device.h"
+#include "cwt_route.h"
 
 namespace spyfft {
+
+using spycwt::cwt_direct_fits;    // (host side of plan creation; lives with the rest of the route)
 
 struct CwtArgs {
     const float* data;            // (rows x ld) float32
@@ -53,42 +56,6 @@ struct CwtArgs {
     const int* smap;              // scatter kernels: staging row s of a segment -> scale index of the output (nullptr = identity)
     int nscales_out;              // scatter kernels: scales of the output (0 = nscales: every scale is staged)
 };
-
-// Host side of plan creation: may the direct kernels (cwt2d_kernel) write a plan's outputs?  A tile of samples
-// [o0, o0 + V) stores at the slot reached before it, sref = tfloor[o0], plus a 32-bit byte offset (slot - sref) * rowb
-// + channel bytes, and tfloor is only a lower bound of the tile's slots if the slots increase with the samples.  So:
-// slots increasing, and for every block of every group the direct kernels serve, the tile's slot span times `rowb`
-// (bytes from one slot to the next: nscales * nchan * element size) plus `chanb` (nchan * element size) below 2^32.
-// Gapped slots (tpos[n] = 10000 n) make the span far larger than the block.  tpos = nullptr: slot n for sample n.
-// V[0 ... ngroups): outputs per block of each direct group.
-inline bool cwt_direct_fits(const int* tpos, int nsig, const int* V, int ngroups, unsigned long long rowb,
-                            unsigned long long chanb) {
-    constexpr unsigned long long LIM = 1ull << 32;
-    if (rowb >= LIM || chanb >= LIM) return false;
-    if (tpos) {
-        int last = -1;
-        for (int n = 0; n < nsig; ++n)
-            if (tpos[n] >= 0) {
-                if (tpos[n] <= last) return false;
-                last = tpos[n];
-            }
-    }
-    for (int g = 0; g < ngroups; ++g) {
-        if (V[g] < 1) return false;
-        long long last = -1, sref = 0;      // (tfloor as cwt.hip uploads it: the largest slot among samples 0 ... n, >= 0)
-        for (int n = 0; n < nsig; ++n) {
-            if (!tpos) last = n;
-            else if (tpos[n] >= 0) last = tpos[n];
-            const long long fl = last > 0 ? last : 0;
-            if (n % V[g] == 0) sref = fl;
-            if (n % V[g] == V[g] - 1 || n == nsig - 1) {
-                const unsigned long long span = (unsigned long long)(fl - sref);
-                if (span >= LIM || span * rowb + chanb >= LIM) return false;
-            }
-        }
-    }
-    return true;
-}
 
 // per (segment, channel): mean and least-squares slope over the trial rows [lo, hi), in two
 // deterministic stages: partial sums over CWT_TREND_SPLITS slices of the trial (many workgroups in

@@ -1,5 +1,5 @@
 // Small fp64 host FFT (iterative radix-2) used once per plan to build filter spectra
-// (Bluestein chirp filter, Morlet kernel spectra).
+// (Bluestein chirp filter, Morlet kernel spectra), and the twiddle tables the plans upload.
 #pragma once
 #include <cmath>
 #include <utility>
@@ -32,5 +32,18 @@ inline void fft_host(std::vector<double>& re, std::vector<double>& im) {
             }
         }
     }
+}
+
+// the first `count` entries of exp(-2 pi i m / n), as float2 or double2
+template <class T2>
+std::vector<T2> twiddle_table(int n, int count = -1) {
+    const double PI = 3.14159265358979323846264338327950288;
+    std::vector<T2> t(count < 0 ? n : count);
+    for (size_t m = 0; m < t.size(); ++m) {
+        const double ang = -2.0 * PI * (double)m / (double)n;
+        t[m].x = (decltype(T2::x))std::cos(ang);
+        t[m].y = (decltype(T2::x))std::sin(ang);
+    }
+    return t;
 }
 }  // namespace spy

@@ -123,17 +123,7 @@ namespace {
 
 const double PI = 3.14159265358979323846264338327950288;
 
-// the first `count` entries of exp(-2 pi i m / n), as float2 or double2
-template <class T2>
-std::vector<T2> twiddle_table(int n, int count = -1) {
-    std::vector<T2> t(count < 0 ? n : count);
-    for (size_t m = 0; m < t.size(); ++m) {
-        const double ang = -2.0 * PI * (double)m / (double)n;
-        t[m].x = (decltype(T2::x))std::cos(ang);
-        t[m].y = (decltype(T2::x))std::sin(ang);
-    }
-    return t;
-}
+using spy::twiddle_table;
 
 // Bluestein: chirp[n] = exp(-i pi n^2 / nfft) and bhat = FFT_M of the wrapped conjugate chirp, / M.  M1 > 0: bhat in the
 // [k1][k2] order of a four-step transform with M = M1 x M2.

@@ -11,7 +11,7 @@ CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 def sources():
     root = os.path.join(HERE, "..", "..")
     deps = [os.path.join(HERE, "hip_emu.h"), os.path.join(HERE, "emu_m3_widths.h"), os.path.join(HERE, "emu_kernels.cpp"),
-            os.path.join(root, "include", "spyhip.h")]
+            os.path.join(HERE, "cwt_route_text.h"), os.path.join(root, "include", "spyhip.h")]
     csrc = os.path.join(root, "syncopy_amd", "csrc")
     deps += [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
     return deps

@@ -461,67 +461,38 @@ def coh_normalize(csd, output="abs"):
     return out
 
 
-def cwt_plan_tables(nsig, scales, dt, w0, nbmin=1024):
-    """NumPy mirror of the plan construction in syncopy_amd/csrc/cwt.hip."""
-    kers, halo, right = [], 0, 0
-    for sc in scales:
-        M = 10.0 * sc / dt
-        t0, t1 = (-M + 1.0) / 2.0, (M + 1.0) / 2.0
-        L = max(int(np.ceil(t1 - t0)), 1)
-        c = (L - 1) // 2
-        m0, m1 = max(0, c - (nsig - 1)), min(L, c + nsig)
-        m = np.arange(m0, m1, dtype=np.float64)
-        x = (t0 + m) * dt / sc
-        norm = np.sqrt(dt) / (sc * 8.0 * np.pi) * np.pi ** (-0.25)
-        h = norm * np.exp(-0.5 * x * x) * (np.exp(1j * w0 * x) - np.exp(-0.5 * w0 * w0))
-        kers.append((h, c - m0))
-        halo = max(halo, h.size - 1 - (c - m0))
-        right = max(right, c - m0)
-    NB = nbmin
-    while NB < 2 * (halo + right + 1) and NB < 16384:
-        NB *= 2
-    V = NB - halo - right
-    assert V >= 1
-    hs = np.zeros((len(scales), NB), dtype=np.complex128)
-    cshift = np.zeros(len(scales), dtype=np.int32)
-    for s, (h, c) in enumerate(kers):
-        hs[s, :h.size] = h
-        cshift[s] = halo + c
-    hs = np.fft.fft(hs, axis=1) / NB
-    hspec = np.stack([hs.real, hs.imag], axis=-1).astype(np.float32).copy()
-    return NB, V, halo, cshift, hspec
-
-
 def cwt_exec(data, seg_start, trial_lo, trial_hi, nsig, scales, dt, w0=6.0, detrend=-1, output="pow", tpos=None,
-             ntime_out=None, chan_idx=None, accumulate=0, mode=0, nbmin=1024, out=None):
-    """`mode` as cwt.hip combines the kernel variants: bit 0 trial sums on pairs of segments (accumulate=2), bit 1 the direct
-    kernels (1024- / 2048-point blocks, accumulate 0 / 1), bit 2 the channel-major input copy; `nbmin`: the shortest
-    block (build_groups); `out`: the array to store into / add to (a zeroed one by default)."""
+             ntime_out=None, chan_idx=None, accumulate=0, family=None, order=None, sl_cycles=None, direct=True,
+             precision64=False, num_cu=None, stage_budget=None, work_budget=None, out=None, trace=None):
+    """Emulated spyhip_cwt_plan_create* + spyhip_cwt_exec: the emulator samples the taps, asks the route of
+    syncopy_amd/csrc/cwt_route.h for the plan and the steps, and walks them.  family None (Morlet, w0) / "Paul" / "DOG" with
+    `order`, or `sl_cycles` (MorletSL, k_sd = 5); `direct` / `precision64`: spyhip_cwt_plan_set_direct / _set_precision;
+    `num_cu`, `stage_budget`, `work_budget` (bytes): what the route plans for instead of the chip and the library's budgets;
+    `out`: the array to store into / add to (a zeroed one by default); `trace`: a list that receives one line per step."""
     data = np.ascontiguousarray(data, dtype=np.float32)
     ld = data.shape[1]
     nchan = ld if chan_idx is None else len(chan_idx)
     ci = None if chan_idx is None else np.ascontiguousarray(chan_idx, dtype=np.int32)
     ss, tl, th = (np.ascontiguousarray(a, dtype=np.int64) for a in (seg_start, trial_lo, trial_hi))
-    NB, V, halo, cshift, hspec = cwt_plan_tables(nsig, scales, dt, w0, nbmin)
-    log2n = int(np.log2(NB))
-    G = {10: 4, 11: 2}.get(log2n, 1)      # channel pairs per workgroup (packed kernel), 2^14: channels
-    if mode & 2:
-        G = {10: 8, 11: 4}[log2n]         # the direct kernels' workgroups
-    tw = twiddles(NB)
+    sc = np.ascontiguousarray(scales, dtype=np.float64)
+    fam, p0, p1 = (1, sl_cycles, 5.0) if sl_cycles is not None else ({None: 0, "Paul": 2, "DOG": 3}[family], order or w0, 0.0)
     kind = OUT_KINDS[output]
     tp = None if tpos is None else np.ascontiguousarray(tpos, dtype=np.int32)
     nto = nsig if tpos is None else int(ntime_out)
-    shape = (1 if accumulate == 2 else len(ss), nto, len(scales), nchan)
+    shape = (1 if accumulate == 2 else len(ss), nto, len(sc), nchan)
     if out is None:
         out = np.zeros(shape, dtype=np.complex64 if kind == 2 else np.float32)
     assert out.shape == shape and out.flags.c_contiguous and out.dtype == (np.complex64 if kind == 2 else np.float32)
-    rc = lib().emu_cwt(C.c_int(log2n), C.c_int(G), _p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int),
-                       _p(ss, C.c_longlong), _p(tl, C.c_longlong), _p(th, C.c_longlong), C.c_int(len(ss)),
-                       C.c_int(nsig), C.c_int(nchan), C.c_int(len(scales)), _p(tw, C.c_float),
-                       hspec.ctypes.data_as(C.POINTER(C.c_float)), _p(cshift, C.c_int), C.c_int(V), C.c_int(halo),
-                       C.c_int((nsig + V - 1) // V), C.c_int(detrend), C.c_int(kind), _p(tp, C.c_int), C.c_int(nto),
-                       out.ctypes.data_as(C.c_void_p), C.c_int(accumulate), C.c_int(mode))
-    assert rc == 0
+    text = C.create_string_buffer(1 << 16)
+    rc = lib().emu_cwt(_p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int), _p(ss, C.c_longlong), _p(tl, C.c_longlong),
+                       _p(th, C.c_longlong), C.c_int(len(ss)), C.c_int(nsig), C.c_int(nchan), C.c_int(len(sc)),
+                       _p(sc, C.c_double), C.c_double(dt), C.c_int(fam), C.c_double(p0), C.c_double(p1), C.c_int(detrend),
+                       C.c_int(kind), _p(tp, C.c_int), C.c_int(nto), out.ctypes.data_as(C.c_void_p), C.c_int(accumulate),
+                       C.c_int(direct), C.c_int(precision64), C.c_longlong(num_cu or 0), C.c_longlong(stage_budget or 0),
+                       C.c_longlong(work_budget or 0), text, C.c_int(len(text)))
+    assert rc == 0, rc
+    if trace is not None:
+        trace.extend(text.value.decode().splitlines())
     return out
 
 
@@ -545,53 +516,29 @@ def cwt64_taps(nsig, scales, dt, w0=6.0, family=None, order=None, sl_cycles=None
     return out
 
 
-def cwt64_tables(nsig, taps):
-    """NumPy mirror of spyhip_cwt_plan_set_precision: L = 2^m >= max(16, nsig + taps - 1), the length-L twiddles,
-    hspec64 = FFT_L(trimmed taps) / L, the centres."""
-    lmax = max(h.size for h, _ in taps)
-    L = 16
-    while L < nsig + lmax - 1:
-        L *= 2
-    hs = np.zeros((len(taps), L), dtype=np.complex128)
-    for s, (h, _) in enumerate(taps):
-        hs[s, :h.size] = h
-    hs = np.fft.fft(hs, axis=1) / L
-    hspec = np.ascontiguousarray(np.stack([hs.real, hs.imag], axis=-1))
-    centre = np.array([c for _, c in taps], dtype=np.int32)
-    return L, twiddles64(L), hspec, centre
+def cwt_conv_length64(nsig, ntaps):
+    """L of spyhip_cwt_plan_set_precision: 2^m >= max(16, nsig + the longest kernel - 1)."""
+    nt = np.ascontiguousarray(ntaps, dtype=np.int32)
+    f = lib().emu_cwt_conv_length64
+    f.restype = C.c_longlong
+    return f(C.c_int(nsig), _p(nt, C.c_int), C.c_int(nt.size))
 
 
-def cwt64_exec(data, seg_start, trial_lo, trial_hi, nsig, scales, dt, w0=6.0, family=None, order=None, sl_cycles=None,
-               detrend=-1, output="pow", tpos=None, ntime_out=None, chan_idx=None, accumulate=0, per_launch=None,
-               seg_chunk=None, out=None):
-    """Emulated spyhip_cwt_exec of a plan with spyhip_cwt_plan_set_precision(plan, 1) (cwt64_kernel.h): `per_launch`
-    (segment, channel) items per cwt64_kernel launch, `seg_chunk` segments per staging chunk (default: all at once).
-    `out`: the array to store into / add to (accumulate 1 / 2); a zeroed one otherwise."""
-    data = np.ascontiguousarray(data, dtype=np.float32)
-    ld = data.shape[1]
-    nchan = ld if chan_idx is None else len(chan_idx)
-    ci = None if chan_idx is None else np.ascontiguousarray(chan_idx, dtype=np.int32)
-    ss, tl, th = (np.ascontiguousarray(a, dtype=np.int64) for a in (seg_start, trial_lo, trial_hi))
-    nseg = len(ss)
-    L, tw, hspec, centre = cwt64_tables(nsig, cwt64_taps(nsig, scales, dt, w0, family, order, sl_cycles))
-    kind = OUT_KINDS[output]
-    tp = None if tpos is None else np.ascontiguousarray(tpos, dtype=np.int32)
-    nto = nsig if tpos is None else int(ntime_out)
-    shape = (1 if accumulate == 2 else nseg, nto, len(scales), nchan)
-    if out is None:
-        out = np.zeros(shape, dtype=np.complex64 if kind == 2 else np.float32)
-    assert out.shape == shape and out.flags.c_contiguous and out.dtype == (np.complex64 if kind == 2 else np.float32)
-    rc = lib().emu_cwt64(_p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int), _p(ss, C.c_longlong),
-                         _p(tl, C.c_longlong), _p(th, C.c_longlong), C.c_int(nseg), C.c_int(nsig), C.c_int(nchan),
-                         C.c_int(len(scales)), C.c_int(L), _p(tw, C.c_double), _p(hspec, C.c_double), _p(centre, C.c_int),
-                         C.c_int(detrend), C.c_int(kind), _p(tp, C.c_int), C.c_int(nto), out.ctypes.data_as(C.c_void_p),
-                         C.c_int(accumulate), C.c_longlong(per_launch or nseg * nchan), C.c_int(seg_chunk or nseg))
-    assert rc == 0, rc
-    return out
+def cwt64_exec(data, seg_start, trial_lo, trial_hi, nsig, scales, dt, per_launch=None, seg_chunk=None, **kw):
+    """cwt_exec at reference precision (cwt64_kernel.h).  `per_launch` (segment, channel) items per cwt64_kernel launch and
+    `seg_chunk` segments per staging chunk, turned into the byte budgets that make the route choose them."""
+    nchan = np.asarray(data).shape[1] if kw.get("chan_idx") is None else len(kw["chan_idx"])
+    if per_launch:
+        taps = cwt64_taps(nsig, scales, dt, kw.get("w0", 6.0), kw.get("family"), kw.get("order"), kw.get("sl_cycles"))
+        kw.update(num_cu=1, work_budget=per_launch * 3 * 16 * cwt_conv_length64(nsig, [h.size for h, _ in taps]))
+        assert per_launch >= 2                   # (the route launches at least two items per compute unit)
+    if seg_chunk:
+        kw.update(stage_budget=seg_chunk * len(scales) * nchan * nsig * (8 if OUT_KINDS[kw.get("output", "pow")] == 2 else 4))
+    return cwt_exec(data, seg_start, trial_lo, trial_hi, nsig, scales, dt, precision64=True, **kw)
 
 
 def cwt_direct_fits(tpos, nsig, V, rowb, chanb):
-    """cwt_kernel.h: cwt_direct_fits - may the direct kernels write a plan with these slots, block groups and row bytes."""
+    """cwt_route.h: cwt_direct_fits - may the direct kernels write a plan with these slots, block groups and row bytes."""
     tp = None if tpos is None else np.ascontiguousarray(tpos, dtype=np.int32)
     v = np.ascontiguousarray(V, dtype=np.int32)
     f = lib().emu_cwt_direct_fits

@@ -28,8 +28,8 @@ thread_local BlockCtx* t_ctx = nullptr;
 #include "../../syncopy_amd/csrc/mtmfft_mixed.h"
 #include "../../syncopy_amd/csrc/mtmfft_long.h"
 #include "../../syncopy_amd/csrc/mtmfft_declong.h"
-#include "../../syncopy_amd/csrc/cwt_kernel.h"
-#include "../../syncopy_amd/csrc/cwt64_kernel.h"
+#include "../../syncopy_amd/csrc/cwt_launch.h"
+#include "cwt_route_text.h"
 #include "../../syncopy_amd/csrc/granger_kernels.h"
 #include "../../syncopy_amd/csrc/wilson_plus_kernel.h"
 #include "../../syncopy_amd/csrc/mtmfft_dec64_cfg.h"
@@ -712,181 +712,134 @@ int emu_ccov(const float* acc, const float* tw, int nfft, int nchan, int nsample
     return 0;
 }
 
-// CWT: plan tables (kernel spectra, shifts) are built by the Python mirror of cwt.hip.
-int emu_cwt(int log2n, int G, const float* data, long long ld, const int* chan_idx, const long long* seg_start,
-            const long long* trial_lo, const long long* trial_hi, int nseg, int nsig, int nchan, int nscales,
-            const float* tw, const float* hspec, const int* cshift, int V, int halo, int nblocks, int detrend,
-            int out_kind, const int* tpos, int ntime_out, void* out, int accumulate, int mode) {
-    // mode bit 0: trial sums on PAIRS of segments (cwt2_kernel<..., PAIRT>; accumulate = 2); bit 1: the direct kernels
-    // (cwt2d_kernel, 1024- / 2048-point blocks with 8 / 4 channel pairs per workgroup; accumulate 0 / 1); bit 2: the
-    // channel-major input copy (cwt_stage_input_kernel) - as cwt.hip combines them
-    spyfft::CwtArgs a{};
-    a.data = data; a.ld = ld; a.chan_idx = chan_idx; a.seg_start = seg_start; a.trial_lo = trial_lo; a.trial_hi = trial_hi;
-    a.nseg = nseg; a.nsig = nsig; a.nchan = nchan; a.nscales = nscales;
-    a.tw = reinterpret_cast<const float2*>(tw); a.hspec = reinterpret_cast<const float2*>(hspec); a.cshift = cshift;
-    a.V = V; a.halo = halo; a.nblocks = nblocks; a.detrend = detrend; a.out_kind = out_kind; a.tpos = tpos;
-    a.ntime_out = ntime_out; a.out = out; a.accumulate = accumulate;
-    std::vector<double> trend((size_t)nseg * nchan * 2, 0.0);
-    a.trend = trend.data();
-    if (detrend == 0) {                      // as cwt.hip: the reference-order float32 mean
-        emu::launch(dim3((nchan + 63) / 64, nseg), dim3(64), 0, [&] { spyfft::cwt_mean_np_kernel(a, trend.data()); });
-    } else if (detrend > 0) {
-        std::vector<double> part(trend.size() * spyfft::CWT_TREND_SPLITS, 0.0);
-        emu::launch(dim3((nchan + 63) / 64, spyfft::CWT_TREND_SPLITS, nseg), dim3(256), 0,
-                    [&] { spyfft::cwt_trend_partial_kernel(a, part.data()); });
-        emu::launch(dim3((unsigned)(((size_t)nseg * nchan + 255) / 256)), dim3(256), 0,
-                    [&] { spyfft::cwt_trend_final_kernel(a, part.data(), trend.data()); });
+// spyhip_cwt_plan_create* + set_direct / set_precision + spyhip_cwt_exec for the emulated kernels: the taps, the plan and the
+// steps of cwt_route.h (the ones cwt.hip uploads and launches), walked with emu::launch on host buffers.  family, p0, p1:
+// spycwt::sample_taps; num_cu and the two byte budgets as spycwt::ExecQuery (<= 0: the library's).  `trace`: one line per
+// step (cwt_route_text.h).  Returns the route's error code.
+int emu_cwt(const float* data, long long ld, const int* chan_idx, const long long* seg_start, const long long* trial_lo,
+            const long long* trial_hi, int nseg, int nsig, int nchan, int nscales, const double* scales, double dt, int family,
+            double p0, double p1, int detrend, int out_kind, const int* tpos, int ntime_out, void* out, int accumulate,
+            int direct, int precision64, long long num_cu, long long stage_budget, long long work_budget, char* trace, int cap) {
+    using namespace spycwt;
+    std::vector<Taps> taps;
+    std::vector<int> ntaps, centre;
+    for (int s = 0; s < nscales; ++s) {
+        taps.push_back(sample_taps(family, p0, p1, scales[s], dt, nsig));
+        ntaps.push_back((int)taps[s].re.size());
+        centre.push_back(taps[s].c);
     }
-    const bool pairt = (mode & 1) != 0, direct = (mode & 2) != 0;
-    std::vector<float> xt;
-    if (mode & 4) {
-        xt.assign((size_t)nseg * nchan * nsig, 0.f);
-        emu::launch(dim3((nsig + 63) / 64, (nchan + 63) / 64, nseg), dim3(256), 0, [&] { spyfft::cwt_stage_input_kernel(a, xt.data()); });
-        a.xt = xt.data();
-    }
-    const int outk = out_kind == SPYHIP_OUT_FOURIER ? 2 : (out_kind == SPYHIP_OUT_POW ? 0 : 1);
-    if (direct) {
-        std::vector<int> fl(nsig, 0);
-        if (tpos) {
-            int last = -1;
-            for (int n = 0; n < nsig; ++n) { if (tpos[n] >= 0) last = tpos[n]; fl[n] = last > 0 ? last : 0; }
-            a.tfloor = fl.data();
-        }
-        const unsigned dgrid = (unsigned)nseg * (unsigned)(((nchan + 1) / 2 + G - 1) / G) * (unsigned)nblocks;
-#define CWT2D_CASE(L, GG) \
-        if (log2n == L && G == GG) { \
-            using C = spyfft::Cfg2<L, GG>; \
-            if (outk == 2) emu::launch(dim3(dgrid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::cwt2d_kernel<L, GG, 2>(a); }); \
-            else if (outk == 0) emu::launch(dim3(dgrid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::cwt2d_kernel<L, GG, 0>(a); }); \
-            else emu::launch(dim3(dgrid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::cwt2d_kernel<L, GG, 1>(a); }); \
-            return 0; \
-        }
-        CWT2D_CASE(10, 8) CWT2D_CASE(11, 4)
-#undef CWT2D_CASE
-        return -1;
-    }
-    const int nsets = pairt ? (nseg + 1) / 2 : nseg;              // staging row sets
-    const int nunit = pairt ? nchan : (log2n <= 13 ? (nchan + 1) / 2 : nchan);      // packed kernel: channel pairs / (PAIRT) channels
-    const unsigned grid = (unsigned)nsets * (unsigned)((nunit + G - 1) / G) * (unsigned)nblocks;
-    // one chunk holding every segment (cwt.hip sizes chunks by memory; the kernels are the same)
-    std::vector<float> stage((size_t)nsets * nscales * nchan * nsig * (outk == 2 ? 2 : 1), 0.f);
-    a.stage = stage.data();
-    a.seg0 = 0;
-    const dim3 sgrid((nsig + 63) / 64, nscales, accumulate == 2 ? 1 : nseg);
-    if (pairt) {
-        if (accumulate != 2 || log2n > 13) return -1;
-        spyfft::CwtArgs sc = a;
-        sc.nseg = nsets;                                           // the transposition pass adds row SETS
-#define CWT2P_CASE(L, GG) \
-        if (log2n == L && G == GG) { \
-            using C = spyfft::Cfg2<L, GG>; \
-            if (outk == 2) emu::launch(dim3(grid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::cwt2_kernel<L, GG, 2, true>(a); }); \
-            else if (outk == 0) emu::launch(dim3(grid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::cwt2_kernel<L, GG, 0, true>(a); }); \
-            else emu::launch(dim3(grid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::cwt2_kernel<L, GG, 1, true>(a); }); \
-            if (outk == 2) emu::launch(sgrid, dim3(256), 0, [&] { spyfft::cwt_scatter_kernel<float2>(sc); }); \
-            else emu::launch(sgrid, dim3(256), 0, [&] { spyfft::cwt_scatter_kernel<float>(sc); }); \
-            return 0; \
-        }
-        CWT2P_CASE(10, 4) CWT2P_CASE(11, 2) CWT2P_CASE(12, 1) CWT2P_CASE(13, 1)
-#undef CWT2P_CASE
-        return -1;
-    }
-#define CWT_CASE(L, GG) \
-    if (log2n == L && G == GG) { \
-        using C = spyfft::Cfg<L, GG>; \
-        if (outk == 2) emu::launch(dim3(grid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::cwt_kernel<L, GG, 2>(a); }); \
-        else if (outk == 0) emu::launch(dim3(grid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::cwt_kernel<L, GG, 0>(a); }); \
-        else emu::launch(dim3(grid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::cwt_kernel<L, GG, 1>(a); }); \
-        if (outk == 2) emu::launch(sgrid, dim3(256), 0, [&] { spyfft::cwt_scatter_kernel<float2>(a); }); \
-        else emu::launch(sgrid, dim3(256), 0, [&] { spyfft::cwt_scatter_kernel<float>(a); }); \
-        return 0; \
-    }
-    CWT_CASE(14, 1)
-#undef CWT_CASE
-#define CWT2_CASE(L, GG) \
-    if (log2n == L && G == GG) { \
-        using C = spyfft::Cfg2<L, GG>; \
-        if (outk == 2) emu::launch(dim3(grid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::cwt2_kernel<L, GG, 2>(a); }); \
-        else if (outk == 0) emu::launch(dim3(grid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::cwt2_kernel<L, GG, 0>(a); }); \
-        else emu::launch(dim3(grid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::cwt2_kernel<L, GG, 1>(a); }); \
-        if (outk == 2) emu::launch(sgrid, dim3(256), 0, [&] { spyfft::cwt_scatter_kernel<float2>(a); }); \
-        else emu::launch(sgrid, dim3(256), 0, [&] { spyfft::cwt_scatter_kernel<float>(a); }); \
-        return 0; \
-    }
-    CWT2_CASE(10, 4) CWT2_CASE(11, 2) CWT2_CASE(12, 1) CWT2_CASE(13, 1)
-#undef CWT2_CASE
-    return -1;
-}
-
-// CWT at reference precision (spyhip_cwt_exec with spyhip_cwt_plan_set_precision(plan, 1)): the trend kernels, cwt64_kernel
-// in launches of `per_launch` (segment, channel) items (cwt.hip: ~2 GiB of work arrays each), chunks of `seg_chunk`
-// segments (cwt.hip: ~4 GiB of staging each), and the transposition pass cwt.hip picks.  Tables (tw64, hspec64 with 1/L
-// folded in, centre) are built by the Python mirror of spyhip_cwt_plan_set_precision; the radix schedule here.
-int emu_cwt64(const float* data, long long ld, const int* chan_idx, const long long* seg_start, const long long* trial_lo,
-              const long long* trial_hi, int nseg, int nsig, int nchan, int nscales, int L, const double* tw64,
-              const double* hspec64, const int* centre, int detrend, int out_kind, const int* tpos, int ntime_out, void* out,
-              int accumulate, long long per_launch, int seg_chunk) {
-    spyfft::CwtArgs a{};
-    a.data = data; a.ld = ld; a.chan_idx = chan_idx; a.seg_start = seg_start; a.trial_lo = trial_lo; a.trial_hi = trial_hi;
-    a.nseg = nseg; a.nsig = nsig; a.nchan = nchan; a.nscales = nscales; a.nscales_total = nscales;
-    a.detrend = detrend; a.out_kind = out_kind; a.tpos = tpos; a.ntime_out = ntime_out; a.out = out; a.accumulate = accumulate;
-    std::vector<double> trend((size_t)nseg * nchan * 2, 0.0);
-    if (detrend >= 0) {
-        a.trend = trend.data();
-        if (detrend == 0) {
-            emu::launch(dim3((nchan + 63) / 64, nseg), dim3(64), 0, [&] { spyfft::cwt_mean_np_kernel(a, trend.data()); });
-        } else {
-            std::vector<double> part(trend.size() * spyfft::CWT_TREND_SPLITS, 0.0);
-            emu::launch(dim3((nchan + 63) / 64, spyfft::CWT_TREND_SPLITS, nseg), dim3(256), 0,
-                        [&] { spyfft::cwt_trend_partial_kernel(a, part.data()); });
-            emu::launch(dim3((unsigned)(((size_t)nseg * nchan + 255) / 256)), dim3(256), 0,
-                        [&] { spyfft::cwt_trend_final_kernel(a, part.data(), trend.data()); });
-        }
-    }
+    const Plan pl = plan_route(nsig, nchan, out_kind, detrend, ntaps, centre, tpos);
+    if (pl.err) return pl.err;
+    ExecQuery q;
+    q.nseg = nseg; q.accumulate = accumulate; q.direct = direct && pl.direct_ok; q.precision64 = precision64 != 0;
+    if (num_cu > 0) q.num_cu = num_cu;
+    if (stage_budget > 0) q.stage_budget = (size_t)stage_budget;
+    if (work_budget > 0) q.work_budget = (size_t)work_budget;
     spyfft::Cwt64Args fa{};
-    fa.L = L;
-    if (!spywil::plus_plan(L, &fa.plan)) return -2;
-    fa.tw64 = reinterpret_cast<const double2*>(tw64);
-    fa.hspec64 = reinterpret_cast<const double2*>(hspec64);
-    fa.centre = centre;
-    const int outk = out_kind == SPYHIP_OUT_FOURIER ? 2 : (out_kind == SPYHIP_OUT_POW ? 0 : 1);
-    const size_t esz = outk == 2 ? 8 : 4;
-    if (seg_chunk < 1 || per_launch < 1) return -1;
-    const int chunk = std::min(seg_chunk, nseg);
-    std::vector<char> stage((size_t)chunk * nscales * nchan * nsig * esz);
-    std::vector<double2> work((size_t)per_launch * 3 * L);
-    fa.work = work.data();
-    for (int s0 = 0; s0 < nseg; s0 += chunk) {                // as the chunk loop of spyhip_cwt_exec
-        const int ns = std::min(chunk, nseg - s0);
-        spyfft::CwtArgs c = a;
-        c.seg0 = s0;
-        c.seg_start = a.seg_start + s0;
-        c.trial_lo = a.trial_lo + s0;
-        c.trial_hi = a.trial_hi + s0;
-        if (a.trend) c.trend = a.trend + (size_t)s0 * nchan * 2;
-        c.nseg = ns;
-        c.stage = stage.data();
-        fa.c = c;
-        const long long items = (long long)ns * nchan;
-        for (long long w0 = 0; w0 < items; w0 += per_launch) {
-            fa.wg0 = w0;
-            const unsigned g = (unsigned)std::min<long long>(per_launch, items - w0);
-            if (outk == 2) emu::launch(dim3(g), dim3(256), 0, [&] { spyfft::cwt64_kernel<2>(fa); });
-            else if (outk == 0) emu::launch(dim3(g), dim3(256), 0, [&] { spyfft::cwt64_kernel<0>(fa); });
-            else emu::launch(dim3(g), dim3(256), 0, [&] { spyfft::cwt64_kernel<1>(fa); });
-        }
-        const dim3 sg((nsig + 63) / 64, nscales, accumulate == 2 ? 1 : ns);
-        const bool wide = esz == 4 && (nsig & 3) == 0 && nsig >= 1024;
-        if (esz == 8) emu::launch(sg, dim3(256), 0, [&] { spyfft::cwt_scatter_kernel<float2>(c); });
-        else if (wide) emu::launch(dim3((nsig + 255) / 256, sg.y, sg.z), dim3(256), 0, [&] { spyfft::cwt_scatter_wide_kernel(c); });
-        else emu::launch(sg, dim3(256), 0, [&] { spyfft::cwt_scatter_kernel<float>(c); });
+    std::vector<double2> tw64, hspec64;
+    if (q.precision64) {                     // spyhip_cwt_plan_set_precision
+        q.L64 = conv_length64(nsig, ntaps);
+        if (q.L64 > MAX_L64 || !spywil::plus_plan((int)q.L64, &fa.plan)) return -3;
+        tw64 = spy::twiddle_table<double2>((int)q.L64);
+        hspec64.resize((size_t)nscales * q.L64);
+        for (int s = 0; s < nscales; ++s) kernel_spectrum(taps[s], 0, taps[s].re.size(), (size_t)q.L64, &hspec64[(size_t)s * q.L64]);
+        fa.L = (int)q.L64; fa.tw64 = tw64.data(); fa.hspec64 = hspec64.data(); fa.centre = pl.centre.data();
     }
-    return 0;
+    const ExecRoute r = exec_route(pl, q);
+    if (trace) {
+        std::string t;
+        for (const Step& s : r.steps) t += render_step(pl, r, s) + "\n";
+        std::snprintf(trace, cap, "%s", t.c_str());
+    }
+    // the tables upload_groups of cwt.hip builds for the group set in use
+    const std::vector<Group>& groups = r.sum_set ? pl.groups_sum : pl.groups;
+    struct Tables { std::vector<float2> tw, hspec; };
+    std::vector<Tables> tables(q.precision64 ? 0 : groups.size());
+    for (size_t gi = 0; gi < tables.size(); ++gi) {
+        const Group& g = groups[gi];
+        const size_t NB = (size_t)1 << g.log2n;
+        tables[gi].tw = spy::twiddle_table<float2>((int)NB);
+        tables[gi].hspec.resize(g.nscales() * NB);
+        for (int k = 0; k < g.nscales(); ++k) {
+            const Taps& t = taps[g.scale_ids[k]];
+            const bool piece = g.long_idx >= 0;
+            kernel_spectrum(t, piece ? g.tap0 : 0, piece ? g.ntaps : t.re.size(), NB, &tables[gi].hspec[k * NB]);
+        }
+    }
+    std::vector<double> trend(r.trend), trend_part(r.trend * TREND_SPLITS);
+    std::vector<char> stage(r.stage_bytes);
+    std::vector<float2> stage_long(r.stage_long);
+    std::vector<float> xt(r.xt);
+    std::vector<double2> work(r.work64);
+    std::vector<int> fl;
+    spyfft::CwtArgs a{};
+    a.data = data; a.ld = ld; a.chan_idx = chan_idx;
+    a.nsig = nsig; a.nchan = nchan; a.nscales = nscales; a.nscales_total = nscales;
+    a.detrend = detrend; a.out_kind = out_kind; a.tpos = tpos;
+    if (tpos) { fl = tfloor(tpos, nsig); a.tfloor = fl.data(); }
+    a.ntime_out = tpos ? ntime_out : nsig; a.out = out; a.accumulate = accumulate;
+    a.stage = stage.data();
+    fa.work = work.data();
+    for (const Step& s : r.steps) {
+        spyfft::CwtArgs c = a;
+        c.seg0 = s.seg0; c.nseg = s.nseg;
+        c.seg_start = seg_start + s.seg0; c.trial_lo = trial_lo + s.seg0; c.trial_hi = trial_hi + s.seg0;
+        if (detrend >= 0) c.trend = trend.data() + (size_t)s.seg0 * nchan * 2;
+        if (r.xt && s.kind == StepKind::TRANSFORM) c.xt = xt.data();
+        const dim3 grid((unsigned)s.gx, (unsigned)s.gy, (unsigned)s.gz);
+        switch (s.kind) {
+            case StepKind::MEAN_NP: emu::launch(grid, dim3(64), 0, [&] { spyfft::cwt_mean_np_kernel(c, trend.data()); }); break;
+            case StepKind::TREND:
+                emu::launch(grid, dim3(256), 0, [&] { spyfft::cwt_trend_partial_kernel(c, trend_part.data()); });
+                emu::launch(dim3((unsigned)(((size_t)nseg * nchan + 255) / 256)), dim3(256), 0,
+                            [&] { spyfft::cwt_trend_final_kernel(c, trend_part.data(), trend.data()); });
+                break;
+            case StepKind::INPUT_COPY: emu::launch(grid, dim3(256), 0, [&] { spyfft::cwt_stage_input_kernel(c, xt.data()); }); break;
+            case StepKind::CWT64:
+                fa.c = c; fa.wg0 = s.wg0;
+                with_cwt64_kernel(s.outk, [&](auto kern) { emu::launch(grid, dim3(256), 0, [&] { kern(fa); }); return 0; });
+                break;
+            case StepKind::TRANSFORM: {
+                const Group& gr = groups[s.group];
+                c.nscales = gr.nscales();
+                c.sidx = s.sidx == Sidx::COMPACT ? gr.sidx_stage.data() : gr.sidx.data();
+                c.nscales_total = s.nrows;
+                c.tw = tables[s.group].tw.data(); c.hspec = tables[s.group].hspec.data(); c.cshift = gr.cshift.data();
+                c.V = gr.V; c.halo = gr.halo; c.nblocks = gr.nblocks;
+                c.stage_add = s.add;
+                if (s.target == Target::LONG_SIDE) c.stage = stage_long.data();
+                const int rc = with_transform_kernel(gr.log2n, s.engine, s.outk, [&](auto kern, int threads, size_t lds) {
+                    emu::launch(grid, dim3(threads), lds, [&] { kern(c); });
+                    return 0;
+                });
+                if (rc) return rc;
+                break;
+            }
+            case StepKind::LONG_CONVERT:
+                emu::launch(grid, dim3(256), 0, [&] {
+                    spyfft::cwt_long_convert_kernel(stage_long.data(), s.sidx == Sidx::COMPACT ? pl.lrow.data() : pl.long_scales.data(),
+                                                    (int)pl.long_scales.size(), s.nseg, s.nrows, nchan, nsig, out_kind,
+                                                    reinterpret_cast<float*>(stage.data()));
+                });
+                break;
+            case StepKind::SCATTER:
+                c.nseg = s.nsets; c.nscales = s.nrows;
+                if (s.compact) { c.smap = pl.staged.data(); c.nscales_out = nscales; }
+                with_scatter_kernel(s.scatter, [&](auto kern) { emu::launch(grid, dim3(256), 0, [&] { kern(c); }); return 0; });
+                break;
+        }
+    }
+    return r.err;
 }
 
-// the plan-creation rule of cwt.hip for the direct kernels (cwt_kernel.h)
+// L of spyhip_cwt_plan_set_precision for these tap counts
+long long emu_cwt_conv_length64(int nsig, const int* ntaps, int nscales) {
+    return spycwt::conv_length64(nsig, std::vector<int>(ntaps, ntaps + nscales));
+}
+
+// the plan-creation rule for the direct kernels (cwt_route.h)
 int emu_cwt_direct_fits(const int* tpos, int nsig, const int* V, int ngroups, unsigned long long rowb, unsigned long long chanb) {
-    return spyfft::cwt_direct_fits(tpos, nsig, V, ngroups, rowb, chanb) ? 1 : 0;
+    return spycwt::cwt_direct_fits(tpos, nsig, V, ngroups, rowb, chanb) ? 1 : 0;
 }
 
 // ---- Wilson / Granger kernels, one entry per kernel (the Python test re-creates the host loop of granger.hip)

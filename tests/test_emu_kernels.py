@@ -322,16 +322,18 @@ def test_ccov_kernel(C, N, norm):
 @pytest.mark.parametrize("nsig,scales,detrend,output", [
     (700, [0.05, 0.02, 0.004], 0, "pow"),            # kernels of 500/200/40 taps, one block
     (3000, [0.03, 0.006], 1, "fourier"),             # several overlap-save blocks
-    (300, [0.2, 0.01], -1, "abs"),                   # kernel (2000 taps) much longer than the signal: trimmed
+    (300, [0.2, 0.03, 0.01], -1, "abs"),             # kernel (2000 taps) much longer than the signal: trimmed
 ])
 def test_cwt_kernel(nsig, scales, detrend, output):
+    """The staged kernels (a plan with set_direct(False)) on the blocks the plan's rule gives these scales: 2048 + 1024,
+    2048 + 1024, 4096 + 2048 + 1024 points."""
     rng = np.random.default_rng(nsig)
     nchan = 3
     data = rng.normal(size=(nsig + 40, nchan)).astype("f4") + 0.5
     pre0 = 7                                          # pre-selection starts inside the trial
     ss, lo, hi = np.array([pre0 + 5]), np.array([5]), np.array([5 + nsig + 20])
     scales = np.asarray(scales)
-    out = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, detrend, output)[0]
+    out = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, detrend, output, direct=False)[0]
     trial = O.detrend(np.array(data[5:5 + nsig + 20]), None if detrend < 0 else detrend)
     ref = O.convert_output(O.cwt(trial[pre0:pre0 + nsig], 1000.0, scales).transpose(1, 0, 2), output)
     assert_parity(out, ref, what="cwt")
@@ -342,22 +344,25 @@ def test_cwt_kernel(nsig, scales, detrend, output):
 def test_cwt_direct_kernels(output, nbmin, nchan):
     """cwt2d_kernel (round 6): the transform kernel writes the (time, scale, channel) layout itself - 1024- and 2048-point
     blocks, an odd channel count (padded pair, scalar stores), plain and accumulating (out[b] += segment b) calls, a
-    post-selection of samples, the channel-major input copy in front of it."""
+    post-selection of samples, the channel-major input copy in front of it.  `nbmin`: the block length the plan's rule
+    gives both scales (2048 points: 256 to 511 taps)."""
     rng = np.random.default_rng(nbmin + nchan)
     nsig, T = 1400, 2
     data = rng.normal(size=(T * nsig + 30, nchan)).astype("f4") + 1.5
     ss = np.array([10, nsig + 20])
     lo, hi = ss.copy(), ss + nsig
-    scales = np.array([0.012, 0.004])
+    scales = np.array({1024: [0.012, 0.004], 2048: [0.04, 0.027]}[nbmin])
     ref = np.stack([O.convert_output(O.cwt(O.detrend(np.array(data[a:a + nsig]), 0), 1000.0, scales).transpose(1, 0, 2), output)
                     for a in ss])
-    for mode in (2, 2 | 4):
-        out = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, mode=mode, nbmin=nbmin)
-        assert_parity(out, ref, what=f"direct cwt, mode {mode}")
+    trace = []
+    out = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, trace=trace)
+    assert [t.split()[0] for t in trace] == ["cwt_mean_np", "cwt_stage_input", "cwt2d<%d,%d,%d>" % (
+        {1024: 10, 2048: 11}[nbmin], {1024: 8, 2048: 4}[nbmin], 2 if output == "fourier" else 0)]
+    assert_parity(out, ref, what="direct cwt")
     keep = np.r_[0:3, 5:1300:9, 1023, 1024, 1399]
     tpos = np.full(nsig, -1, dtype=np.int32)
     tpos[keep] = np.arange(keep.size)
-    sel = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=keep.size, mode=2 | 4, nbmin=nbmin)
+    sel = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=keep.size)
     assert_parity(sel, ref[:, keep], what="direct cwt, selected samples")
 
 
@@ -365,18 +370,93 @@ def test_cwt_direct_kernels(output, nbmin, nchan):
 @pytest.mark.parametrize("T", [4, 5])
 def test_cwt_trial_sums_on_pairs_of_trials(output, T):
     """cwt2_kernel<..., PAIRT> (round 6): one channel of TWO consecutive trials in the packed halves, their sum staged;
-    an odd trial count leaves the last pair half empty; with and without the channel-major input copy; 2048-point
-    blocks as the trial-sum policy of cwt.hip picks longer ones."""
+    an odd trial count leaves the last pair half empty; 1024-point blocks, and a plan with a 2048-point group next to one."""
     rng = np.random.default_rng(T)
     nsig, nchan = 900, 3
     data = rng.normal(size=(T * nsig, nchan)).astype("f4") - 0.7
     ss = np.arange(T) * nsig
-    scales = np.array([0.015, 0.005])
-    ref = sum(O.convert_output(O.cwt(O.detrend(np.array(data[a:a + nsig]), 0), 1000.0, scales).transpose(1, 0, 2).astype(np.complex128), output)
-              for a in ss)[None]
-    for mode, nbmin in ((1, 1024), (1 | 4, 1024), (1 | 4, 2048)):
-        out = E.cwt_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, 6.0, 0, output, accumulate=2, mode=mode, nbmin=nbmin)
-        assert_parity(out, ref.astype(out.dtype), what=f"pair sums, mode {mode}, blocks >= {nbmin}")
+    outk = 2 if output == "fourier" else 0
+    for scales, kernels in (([0.015, 0.005], ["cwt2<10,4,%d,pairs>" % outk]),
+                            ([0.03, 0.015, 0.005], ["cwt2<10,4,%d,pairs>" % outk, "cwt2<11,2,%d,pairs>" % outk])):
+        scales = np.array(scales)
+        ref = sum(O.convert_output(O.cwt(O.detrend(np.array(data[a:a + nsig]), 0), 1000.0, scales).transpose(1, 0, 2).astype(np.complex128), output)
+                  for a in ss)[None]
+        trace = []
+        out = E.cwt_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, 6.0, 0, output, accumulate=2, trace=trace)
+        assert [t.split()[0] for t in trace if t.startswith("cwt2")] == kernels
+        assert_parity(out, ref.astype(out.dtype), what=f"pair sums, {len(kernels)} groups")
+
+
+# ---- whole plans through the route of cwt_route.h: several groups, pieces, the sum sets, chunks -----------------------------
+def _cwt_plan_case(nsig, freqs_or_scales, nseg, output, accumulate=0, nchan=3, seed=0, **kw):
+    """(emulated output, oracle reference, step lines) of a plan with constant detrending on `nseg` trials of nsig samples."""
+    rng = np.random.default_rng(seed + nsig)
+    data = rng.normal(size=(nseg * nsig + 20, nchan)).astype("f4") + 0.8
+    ss = np.arange(nseg) * nsig + 10
+    scales = np.asarray(freqs_or_scales, dtype=np.float64)
+    ref = np.stack([O.convert_output(O.cwt(O.detrend(np.array(data[a:a + nsig]), 0), 1000.0, scales).transpose(1, 0, 2), output)
+                    for a in ss])
+    if accumulate == 2:
+        ref = ref.astype(np.complex128 if output == "fourier" else np.float64).sum(axis=0, keepdims=True)
+    trace = []
+    out = E.cwt_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, 6.0, 0, output, accumulate=accumulate, trace=trace, **kw)
+    return out, ref.astype(out.dtype), trace
+
+
+def _kernels(trace):
+    return [t.split()[0] for t in trace if t.startswith(("cwt<", "cwt2<", "cwt2d<", "cwt_long", "cwt_scatter"))]
+
+
+def _morlet_scales(freqs):
+    return (6 + np.sqrt(38)) / (4 * np.pi * np.asarray(freqs, dtype=np.float64))
+
+
+@pytest.mark.parametrize("output", ["pow", "fourier"])
+def test_cwt_plan_with_three_groups(output):
+    """1024- and 2048-point direct groups next to a staged 4096-point group: the compact staging rows (sidx_stage, smap,
+    nscales_out) run beside the direct kernels.  120, 400 and 800 taps."""
+    out, ref, trace = _cwt_plan_case(1400, [0.012, 0.08, 0.04], 2, output)
+    k = 2 if output == "fourier" else 0
+    assert _kernels(trace) == ["cwt2d<10,8,%d>" % k, "cwt2d<11,4,%d>" % k, "cwt2<12,1,%d>" % k,
+                               "cwt_scatter<%s>" % ("float2" if k else "wide")]
+    assert "sidx compact rows 1 -> stage" in trace[4] and "rows 1 compact" in trace[5]
+    assert_parity(out, ref, what="three groups")
+
+
+@pytest.mark.parametrize("output", ["pow", "fourier"])
+@pytest.mark.parametrize("accumulate,nseg", [(0, 1), (2, 3)])
+def test_cwt_plan_with_a_kernel_longer_than_a_block(output, accumulate, nseg):
+    """0.9 Hz on 4100 samples: 8199 taps after trimming, pieces of 8192 + 7 - the adding piece, the complex side buffer and
+    its conversion (real outputs), the scale's own staging rows (complex ones).  As a trial sum of 3 trials the plan falls
+    back from pairs of trials (the 16384-point kernel is not packed) to the per-segment groups."""
+    out, ref, trace = _cwt_plan_case(4100, _morlet_scales([0.9, 20]), nseg, output, accumulate, nchan=2)
+    k = 2 if output == "fourier" else 0
+    want = ["cwt2d<11,4,%d>" % k if accumulate == 0 else "cwt2<11,2,%d>" % k, "cwt<14,1,2>", "cwt<14,1,2>"]
+    want += (["cwt_long_convert"] if k == 0 else []) + ["cwt_scatter<%s>" % ("float2" if k else "wide")]
+    assert _kernels(trace) == want
+    assert [" add " in t for t in trace if t.startswith("cwt<14")] == [False, True]
+    assert_parity(out, ref, what=f"pieces, accumulate {accumulate}")
+
+
+@pytest.mark.parametrize("output", ["pow", "fourier"])
+def test_cwt_trial_sums_of_long_signals_take_their_own_groups(output):
+    """4100 samples, 20 and 70 Hz (485 and 139 taps: 2048- and 1024-point direct blocks per segment) as a sum of 3 trials:
+    both scales on a 4096-point group of the sum set, on pairs of trials, the last pair half empty."""
+    out, ref, trace = _cwt_plan_case(4100, _morlet_scales([20, 70]), 3, output, 2, nchan=2)
+    k = 2 if output == "fourier" else 0
+    assert _kernels(trace) == ["cwt2<12,1,%d,pairs>" % k, "cwt_scatter<%s>" % ("float2" if k else "wide")]
+    assert "sum group 0" in trace[2] and "sets 2 rows 2" in trace[3]
+    assert_parity(out, ref, what="own sum groups")
+
+
+def test_cwt_float32_plan_in_chunks():
+    """A staging budget of 5 segments: 13 segments run as chunks of 5, 5 and 3 (seg0 > 0: the segment tables, the trend and
+    the output rows move with the chunk)."""
+    nsig, nchan, scales = 300, 2, [0.02, 0.004]
+    out, ref, trace = _cwt_plan_case(nsig, scales, 13, "abs", direct=False, nchan=nchan,
+                                     stage_budget=5 * len(scales) * nchan * nsig * 4 + 100)
+    assert [t.split()[2] for t in trace if t.startswith("cwt_scatter")] == ["0+5", "5+5", "10+3"]
+    assert_parity(out, ref, what="three chunks")
 
 
 # ---- K3 at reference precision (cwt64_kernel.h) and the direct kernels' slot bound ------------------------------------
@@ -430,7 +510,7 @@ def test_cwt64_kernel_lengths():
     assert taps < 500
     cases += [(512 - taps + 1, np.array([0.02, 0.005]), 512), (512 - taps + 2, np.array([0.02, 0.005]), 1024)]
     for nsig, scales, L in cases:
-        Lp = E.cwt64_tables(nsig, E.cwt64_taps(nsig, scales, 1e-3))[0]
+        Lp = E.cwt_conv_length64(nsig, [h.size for h, _ in E.cwt64_taps(nsig, scales, 1e-3)])
         if L is not None:
             assert Lp == L, (nsig, Lp, L)
         else:
@@ -503,7 +583,7 @@ def test_cwt64_kernel_wide_transposition():
 
 
 def test_cwt_direct_bound():
-    """cwt_direct_fits (cwt_kernel.h), the plan-creation rule for the direct kernels: slots increasing with the samples,
+    """cwt_direct_fits (cwt_route.h), the plan-creation rule for the direct kernels: slots increasing with the samples,
     and every tile's slot span * rowb + channel bytes below 2^32 (32-bit store offsets from the tile's reference slot)."""
     lim = 1 << 32
     # contiguous slots: the span of a full block is V - 1; a ragged last block spans less
@@ -552,13 +632,13 @@ def test_cwt_direct_kernels_gapped_slots(output):
     nto = 7 * nsig + 5
     ref = np.stack([O.convert_output(O.cwt(O.detrend(np.array(data[a:a + nsig]), 0), 1000.0, scales).transpose(1, 0, 2), output)
                     for a in ss])
-    out = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=nto, mode=2 | 4)
+    out = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=nto)
     assert_parity(out[:, tpos], ref, what="direct cwt, gapped slots")
     gap = np.ones(nto, dtype=bool)
     gap[tpos] = False
     assert not out[:, gap].any()
     base = np.full(out.shape, 0.25, dtype=out.dtype)
-    acc = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=nto, mode=2 | 4,
+    acc = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=nto,
                      accumulate=1, out=base.copy())
     assert np.array_equal(acc[:, gap], base[:, gap])
     assert_parity(acc[:, tpos] - base[:, tpos], ref, what="direct cwt, gapped slots, accumulate 1")

@@ -499,8 +499,8 @@ def test_cwt_direct_kernels_equal_the_staged_path(be, output, C):
     with every scale through the staging buffer and the transposition pass (set_direct(False)): the same arithmetic per
     value up to the compiler's contraction choices (agreement to 2e-6, five times tighter than the parity criterion); trial
     sums differ in summation order as well.  Scales
-    on every block length at once (70 Hz: 1024, 30: 2048, 8: 4096 - staged in either mode), odd channel counts (the
-    padded pair and the unaligned scalar stores), a post-selection of samples."""
+    on several block lengths at once (45, 70, 95 Hz: 1024 points, 30 Hz: 2048, 8 Hz: 1211 taps on 8192-point blocks - staged
+    in either mode), odd channel counts (the padded pair and the unaligned scalar stores), a post-selection of samples."""
     rng = np.random.default_rng(17)
     nsig, T = 3000, 5
     x = rng.normal(size=(T * nsig, C)).astype(np.float32) + 3.0
@@ -537,7 +537,7 @@ def test_cwt_direct_kernels_equal_the_staged_path(be, output, C):
 
 def test_cwt_trial_sums_long_signals_own_block_groups(be):
     """Trial sums of signals of 4096 samples and more run on their own block groups (at least 4096 points per block,
-    spyhip_cwt_exec: build_groups) with one channel of TWO trials per packed thread: 128 channels x 4500 samples x 37
+    cwt_route.h: Plan::groups_sum) with one channel of TWO trials per packed thread: 128 channels x 4500 samples x 37
     trials (an odd count: the last pair is half empty) in two calls, against the float64 sum of the per-trial outputs,
     which come from the 1024- / 2048-point direct kernels."""
     rng = np.random.default_rng(19)
@@ -574,6 +574,27 @@ def test_cwt_kernels_longer_than_one_block(be, output):
         trl = O.detrend(x[t * nsig:(t + 1) * nsig], 0)
         ref = O.convert_output(O.cwt(trl, 1000.0, scales).transpose(1, 0, 2), output)
         assert_parity(got[t], ref, what=f"long cwt kernels, {output}, trial {t}")
+
+
+@pytest.mark.parametrize("output", ["pow", "fourier"])
+def test_cwt_trial_sum_of_a_plan_with_long_kernels(be, output):
+    """A trial sum whose plan holds a 16384-point group and a scale in pieces (4500 samples: 0.9 Hz -> 8999 taps, pieces of
+    8192 + 807; 1.6 Hz -> 6051 taps on 16384-point blocks; 20 Hz -> 2048-point blocks): the 16384-point kernel carries no
+    pairs of trials, so the sum runs unpaired on the per-segment groups, every scale staged.  3 trials in calls of 2 and 1,
+    against the float64 sum of the per-trial outputs."""
+    rng = np.random.default_rng(23)
+    nsig, C, T = 4500, 3, 3
+    data = torch.from_numpy(rng.normal(size=(T * nsig, C)).astype(np.float32) + 0.5).cuda()
+    scales = (1 / np.array([0.9, 1.6, 20.0])) * (6 + np.sqrt(38)) / (4 * np.pi)
+    plan = be.CWTPlan(nsig, C, scales, 1e-3, 6.0, 0, output)
+    st = torch.arange(T, device="cuda", dtype=torch.int64) * nsig
+    total = torch.zeros(plan.out_shape(1), dtype=torch.complex64 if output == "fourier" else torch.float32, device="cuda")
+    for lo, hi in ((0, 2), (2, 3)):
+        s = st[lo:hi].contiguous()
+        plan.execute(data, s, s, s + nsig, out=total, accumulate=2)
+    each = plan.execute(data, st, st, st + nsig)
+    ref = (each.to(torch.complex128) if each.is_complex() else each.double()).sum(dim=0, keepdim=True)
+    assert_parity(total.cpu().numpy(), ref.cpu().numpy().astype(total.cpu().numpy().dtype), what=f"trial sum with long kernels, {output}")
 
 
 def test_blocked_tail_starts_inside_a_frequency(be):
