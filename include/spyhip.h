@@ -39,6 +39,7 @@ typedef struct spyhip_ctx spyhip_ctx;
 typedef struct spyhip_fft_plan spyhip_fft_plan;
 typedef struct spyhip_cwt_plan spyhip_cwt_plan;
 typedef struct spyhip_queue spyhip_queue;
+typedef struct spyhip_hilbert_plan spyhip_hilbert_plan;
 
 /* output conversions = syncopy/shared/const_def.py:25-37 `spectralConversions` */
 enum spyhip_output {
@@ -510,6 +511,21 @@ int spyhip_fir_same(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t nt
  * down-th sample of spyhip_fir_same.  No NaN report; out_d must not be in_d */
 int spyhip_upfirdn(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t ntrials, int64_t nsamp, int64_t nchan,
                    int64_t nout, const double* taps_d, int ntaps, int up, int down);
+
+/* The Hilbert option (hilbert_cF): scipy.signal.hilbert(trial, axis=0), circular over the trial length nsamp with no
+ * padding, followed by spectralConversions[output].  A plan owns the tables of one trial length, 1 ... 2^20 samples
+ * (-3 beyond); which kernel family serves it is decided in csrc/hilbert_route.h and named by ..._kernel_name.
+ * exec (asynchronous, on the context's stream): in_d (ntrials, nsamp, nchan) float32 -> out_d of the same shape,
+ * complex64 for output = SPYHIP_OUT_FOURIER ("complex"), float32 for SPYHIP_OUT_ABS, _REAL, _IMAG, _ANGLE, _ABSREAL and
+ * _ABSIMAG; out_d must not be in_d.  The real part of the analytic signal is the input itself.  A channel of a trial
+ * that holds a non-finite sample (NaN or +-inf: SciPy leaves a mix of the two there) comes out all-NaN and raises
+ * nan_d[trial]; no other channel is touched by it.  Lengths that are no power of two up to 8192 and are longer than
+ * 4096 samples run in complex128 over work arrays in the context's scratch buffer (at most 512 MiB per launch). */
+int spyhip_hilbert_plan_create(spyhip_ctx* ctx, int64_t nsamp, spyhip_hilbert_plan** plan);
+int spyhip_hilbert_exec(spyhip_hilbert_plan* plan, const float* in_d, void* out_d, int64_t ntrials, int64_t nchan,
+                        int output, int* nan_d);
+int spyhip_hilbert_plan_destroy(spyhip_hilbert_plan* plan);
+const char* spyhip_hilbert_plan_kernel_name(const spyhip_hilbert_plan* plan);
 
 /* ---- spy.timelockanalysis (statistics/timelockanalysis.py; statistics/compRoutines.py: cov_cF).  The channel
  * covariance np.cov(trial, ddof=ddof, rowvar=False) of every trial of a batch of equal-length trials: x_d (ntrials, n,

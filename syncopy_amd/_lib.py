@@ -111,6 +111,10 @@ SIGNATURES = {
                                      C.c_int, vp]),
     "spyhip_fir_same": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int, C.c_int, vp]),
     "spyhip_upfirdn": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int, C.c_int, C.c_int]),
+    "spyhip_hilbert_plan_create": (C.c_int, [vp, C.c_int64, C.POINTER(vp)]),
+    "spyhip_hilbert_exec": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int, vp]),
+    "spyhip_hilbert_plan_destroy": (C.c_int, [vp]),
+    "spyhip_hilbert_plan_kernel_name": (C.c_char_p, [vp]),
     "spyhip_cov_f32": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
 }
 

@@ -1303,6 +1303,67 @@ def upfirdn(x, out, taps, up, down):
     return out
 
 
+class HilbertPlan:
+    """spyhip_hilbert_plan: the tables of the analytic-signal kernels for one trial length (csrc/hilbert.hip)."""
+
+    def __init__(self, ctx, nsamp):
+        self.ctx, self.nsamp = ctx, int(nsamp)
+        h = C.c_void_p()
+        check(ctx.lib.spyhip_hilbert_plan_create(ctx.handle, self.nsamp, C.byref(h)), "spyhip_hilbert_plan_create")
+        self.handle = h
+
+    @property
+    def kernel_name(self):
+        return self.ctx.lib.spyhip_hilbert_plan_kernel_name(self.handle).decode()
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self.ctx.lib.spyhip_hilbert_plan_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+HILBERT_MAX_SAMPLES = 1 << 20       # HILBERT_MAX_N of csrc/hilbert_route.h
+MAX_HILBERT_PLANS = 16
+_hilbert_plans = {}                 # device -> {nsamp: HilbertPlan}, the most recently used last
+
+
+def hilbert_plan(nsamp, device=None):
+    """The plan of trial length `nsamp` on `device`, from a per-context cache of the MAX_HILBERT_PLANS most recently used
+    (plans own device tables: a session over many trial lengths must not accumulate them)."""
+    ctx = context(device)
+    cache = _hilbert_plans.setdefault(ctx.device, {})
+    plan = cache.pop(int(nsamp), None)
+    if plan is None:
+        ctx.bind_stream()
+        plan = HilbertPlan(ctx, nsamp)
+        while len(cache) >= MAX_HILBERT_PLANS:
+            cache.pop(next(iter(cache)))        # dicts iterate in insertion order: the first key is the least recent
+    cache[int(nsamp)] = plan
+    return plan
+
+
+def hilbert(x, out, output, nan):
+    """out = spectralConversions[output](scipy.signal.hilbert(x, axis=1)) per trial of x (ntrials, nsamp, nchan) float32:
+    complex64 for output "complex", float32 for "abs", "real", "imag", "absreal", "absimag", "angle"; out is not x.  nan
+    (int32 per trial, zeroed by the caller) is raised for trials that hold a non-finite sample; such a channel comes out
+    all-NaN."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    kind = OUTPUT_KIND[output]
+    assert output != "pow" and output != "fourier", output
+    assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == tuple(x.shape)
+    assert out.dtype == (torch.complex64 if kind == 2 else torch.float32), (out.dtype, output)
+    assert out.data_ptr() != x.data_ptr()
+    assert nan.dtype == torch.int32 and nan.is_contiguous() and nan.numel() == x.shape[0]
+    plan = hilbert_plan(x.shape[1], x.device)
+    plan.ctx.bind_stream()
+    check(plan.ctx.lib.spyhip_hilbert_exec(plan.handle, _ptr(x), _ptr(out), int(x.shape[0]), int(x.shape[2]), kind,
+                                           _ptr(nan)), "spyhip_hilbert_exec")
+    return out
+
+
 # ---- spy.timelockanalysis (csrc/cov.hip) --------------------------------------------------------------------------
 def cov(x, ddof=None, out=None):
     """np.cov(x[t], ddof=ddof, rowvar=False) of every trial of x (ntrials, nsamp, nchan) float32 as float32 (ntrials,

@@ -10,7 +10,8 @@ import weakref
 
 import numpy as np
 
-from ..datatype import AnalogData, CrossSpectralData, SpectralData, selected_channels, selected_trialdefinition
+from ..datatype import (AnalogData, CrossSpectralData, SpectralData, require_real_analog, selected_channels,
+                        selected_trialdefinition)
 from ..shared.const_def import connectivity_outputs, connectivityMethods
 from ..shared.errors import SPYTypeError, SPYValueError, SPYWarning
 from ..shared.kwarg_decorators import attached_selection, unwrap_cfg
@@ -42,6 +43,7 @@ def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi
         raise SPYValueError("'float32', 'reference' or 'auto'", varname="precision", actual=str(precision))
     if not isinstance(data, (AnalogData, SpectralData)) or data.data is None:
         raise SPYValueError("either AnalogData or SpectralData as input", "data", data.__class__.__name__)
+    require_real_analog(data)
     if method not in connectivityMethods:
         raise SPYValueError("one of " + ", ".join(connectivityMethods), varname="method", actual=method)
     if not isinstance(jackknife, bool):

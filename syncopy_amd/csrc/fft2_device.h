@@ -134,7 +134,7 @@ struct Cfg2 {
     static constexpr int ESTRIDE = (T + (PAD ? T / 16 : 0)) * G;       // LDS distance of e -> e+1 (8-byte units)
     static constexpr int PLANE = (N + (PAD ? N / 16 : 0)) * G + G;      // 8-byte units per plane (+G: slot of index N)
     static constexpr size_t LDS_BYTES = (size_t)PLANE * 16; // real plane + imaginary plane
-    static_assert(LOG2N >= 6 && LOG2N <= 13, "supported FFT lengths: 64..8192 (64 and 128 only as factors of a long transform)");
+    static_assert(LOG2N >= 4 && LOG2N <= 13, "supported FFT lengths: 16..8192 (up to 128 unpadded: factors of a long transform, short Hilbert trials)");
     static_assert(NTHREADS >= 64 && NTHREADS <= 1024, "workgroup size");
     static_assert((64 % G) == 0, "G must divide the wave size");
     __device__ static __forceinline__ int idx(int i, int h) { return (i + (PAD ? (i >> 4) : 0)) * G + h; }

@@ -1,5 +1,5 @@
 // Small fp64 host FFT (iterative radix-2) used once per plan to build filter spectra
-// (Bluestein chirp filter, Morlet kernel spectra), and the twiddle tables the plans upload.
+// (Bluestein chirp filter, Morlet kernel spectra), the twiddle tables and the Bluestein tables the plans upload.
 #pragma once
 #include <cmath>
 #include <utility>
@@ -45,5 +45,34 @@ std::vector<T2> twiddle_table(int n, int count = -1) {
         t[m].y = (decltype(T2::x))std::sin(ang);
     }
     return t;
+}
+
+// Bluestein: chirp[n] = exp(-i pi n^2 / nfft) and bhat = FFT_M of the wrapped conjugate chirp, / M.  M1 > 0: bhat in the
+// [k1][k2] order of a four-step transform with M = M1 x M2.
+template <class T2>
+void bluestein_tables(int nfft, int M, int M1, std::vector<T2>* chirp, std::vector<T2>* bhat) {
+    using T = decltype(T2::x);
+    const double PI = 3.14159265358979323846264338327950288;
+    chirp->resize(nfft);
+    std::vector<double> br(M, 0.0), bi(M, 0.0);
+    for (long long n = 0; n < nfft; ++n) {
+        const long long m = (n * n) % (2LL * nfft);  // exact phase reduction
+        const double ang = PI * (double)m / (double)nfft;
+        (*chirp)[n].x = (T)std::cos(ang);
+        (*chirp)[n].y = (T)-std::sin(ang);
+        br[n] = std::cos(ang);
+        bi[n] = std::sin(ang);
+        if (n > 0) { br[M - n] = br[n]; bi[M - n] = bi[n]; }
+    }
+    fft_host(br, bi);
+    bhat->resize(M);
+    if (M1 <= 0) M1 = M;
+    const int M2 = M / M1;
+    for (int k1 = 0; k1 < M1; ++k1)
+        for (int k2 = 0; k2 < M2; ++k2) {
+            const size_t k = (size_t)k1 + (size_t)M1 * k2;
+            (*bhat)[(size_t)k1 * M2 + k2].x = (T)(br[k] / M);
+            (*bhat)[(size_t)k1 * M2 + k2].y = (T)(bi[k] / M);
+        }
 }
 }  // namespace spy

@@ -198,15 +198,16 @@ class AnalogData(_Base):
         return self._device
 
     def adopt_device_result(self, res):
-        """`res`, a (time x channel) float32 tensor a front end computed on the device, becomes this object's data:
-        device_data() hands it out with no round trip, and the host array is fetched when `.data` is first read."""
+        """`res`, a (time x channel) tensor a front end computed on the device (float32; complex64 from the Hilbert
+        option of spy.preprocessing), becomes this object's data: device_data() hands it out with no round trip, and
+        the host array is fetched when `.data` is first read."""
         from .. import backend
 
         def fetch():
             arr = backend.to_host(res)
             self._device_key = self._device_copy_key(arr, res.device, (0, arr.shape[0]))
             return arr
-        self.set_pending(fetch, res.shape, np.float32)
+        self.set_pending(fetch, res.shape, np.complex64 if res.is_complex() else np.float32)
         self._device = res
         self._device_key = None
         self._row_origin = 0
@@ -223,6 +224,13 @@ class AnalogData(_Base):
     def selectdata(self, select=None):
         self.selection = None if select is None else Selection(self, select)
         return self
+
+
+def require_real_analog(data):
+    """AnalogData of complex numbers (spy.preprocessing(..., hilbert="complex")) is an end product: the front ends that
+    work on real time series refuse it instead of reinterpreting its bytes or dropping its imaginary part."""
+    if isinstance(data, AnalogData) and np.dtype(data.data_dtype).kind == "c":
+        raise SPYTypeError(data.data_dtype, varname="data", expected="real-valued AnalogData")
 
 
 class SpectralData(_Base):

@@ -1,20 +1,21 @@
-"""`spy.preprocessing`: detrending, z-scoring, Butterworth and windowed-sinc filtering and rectification of AnalogData
-along time (syncopy/preproc/preprocessing.py with preproc/compRoutines.py), on the device.
+"""`spy.preprocessing`: detrending, z-scoring, Butterworth and windowed-sinc filtering, rectification and the Hilbert
+transform of AnalogData along time (syncopy/preproc/preprocessing.py with preproc/compRoutines.py), on the device.
 
     spy.preprocessing(adata, freq=100)                                        # Butterworth low-pass, order 4, two-pass
     spy.preprocessing(adata, filter_class="firws", filter_type="bs", freq=[49, 51], order=2000)
     spy.preprocessing(adata, filter_class=None, polyremoval=1, zscore=True)
+    spy.preprocessing(adata, filter_type="bp", freq=[8, 12], hilbert="abs")   # band-pass, then the analytic amplitude
 
 The front end validates, designs the filter on the host in float64 (design.py) and turns the request into the
 reference's chain of steps: [detrend, z-score] if zscore, then [detrend, filter] (polyremoval is applied again by the
-filter routine, as there), |.| fused into the last step.  All arithmetic on samples runs in csrc/preproc.hip; there is
-no CPU path.  `compute_method="sequential"` with `routine_classes` swaps in a NumPy/SciPy model of the steps for the
-tests.  Trials of equal length are filtered together, at most CHUNK_BYTES of input at a time, and reach the device by
-the routes of shared/trial_chunks.py; the result stays on the device for a following spy.freqanalysis
-(AnalogData.adopt_device_result).
+filter routine, as there), |.| fused into the last step, or the Hilbert transform as a last step of its own
+(scipy.signal.hilbert over the trial length and the output conversion in one kernel, csrc/hilbert.hip).  All arithmetic
+on samples runs in csrc/preproc.hip and csrc/hilbert.hip; there is no CPU path.  `compute_method="sequential"` with
+`routine_classes` swaps in a NumPy/SciPy model of the steps for the tests.  Trials of equal length are filtered
+together, at most CHUNK_BYTES of input at a time, and reach the device by the routes of shared/trial_chunks.py; the
+result stays on the device for a following spy.freqanalysis (AnalogData.adopt_device_result).
 
-Not implemented: `hilbert=<output>` (raises NotImplementedError after validation).  spy.resampledata lives in
-resampledata.py.
+spy.resampledata lives in resampledata.py.
 """
 import numpy as np
 
@@ -34,6 +35,9 @@ hilbert_outputs = {"abs", "complex", "real", "imag", "absreal", "absimag", "angl
 
 # second-order sections the cascade kernels are compiled for (MAX_SECTIONS of csrc/preproc_kernel.h)
 MAX_SECTIONS = 12
+
+# longest trial the Hilbert kernels take (HILBERT_MAX_N of csrc/hilbert_route.h)
+MAX_HILBERT_SAMPLES = 1 << 20
 
 # bytes of input trials filtered at once (the work buffers on the device are a small multiple of this)
 CHUNK_BYTES = 512 << 20
@@ -72,11 +76,14 @@ def preprocessing(data, filter_class="but", filter_type="lp", freq=None, order=N
     polyremoval  : 0 removes the mean, 1 the least-squares line, ahead of any filter
     zscore       : True standardizes every channel of every trial ahead of the filter
     rectify      : True returns |.| of the result
-    hilbert      : validated, then refused with NotImplementedError (no inverse transform of arbitrary length yet)
+    hilbert      : "abs", "complex", "real", "imag", "absreal", "absimag" or "angle": that conversion of the analytic
+                   signal (scipy.signal.hilbert along time, circular over each trial) of the result; not with `rectify`;
+                   trials of at most 2^20 samples; a channel with a non-finite sample comes out all-NaN for that trial
     select       : in-place selection {"trials", "channel", "latency"}
 
-    Returns float32 AnalogData with the input's dimord, channels and samplerate; `info["nan_trials"]` lists the trials
-    whose input held a NaN when a filter or a detrending ran.  `chan_per_worker` / `parallel` are accepted and ignored."""
+    Returns float32 AnalogData (complex64 for hilbert="complex") with the input's dimord, channels and samplerate;
+    `info["nan_trials"]` lists the trials whose input held a NaN when a filter, a detrending or the Hilbert step ran.
+    `chan_per_worker` / `parallel` are accepted and ignored."""
     check_analog_input(data)
     defaults = dict(filter_class="but", filter_type="lp", freq=None, order=None, direction="twopass", window="hamming",
                     polyremoval=None, zscore=False, rectify=False, hilbert=False)
@@ -162,8 +169,12 @@ def preprocessing(data, filter_class="but", filter_type="lp", freq=None, order=N
         elif polyremoval is not None and zscore is False:
             main = list(detrend)
         if hilbert:
-            raise NotImplementedError(f"hilbert='{hilbert}' is not implemented: it needs an inverse transform of "
-                                      "arbitrary trial length on the device")
+            if lengths.max() > MAX_HILBERT_SAMPLES:     # refused here, ahead of any upload: the plan would refuse too
+                raise SPYValueError(f"trials of at most {MAX_HILBERT_SAMPLES} (2^20) samples for the Hilbert transform",
+                                    varname="data", actual=f"a trial of {int(lengths.max())} samples")
+            if compute_method not in (None, "hip") and "hilbert" not in (routine_classes or {}):
+                raise NotImplementedError(f"hilbert='{hilbert}': the routine table has no 'hilbert' entry")
+            main = (main or []) + [("hilbert", hilbert)]
 
         out = AnalogData(None, samplerate=data.samplerate, dimord=data.dimord)
         if compute_method in (None, "hip"):
@@ -196,7 +207,9 @@ def _model_run(data, rows, pre, main, rectify, ops):
             x = np.asarray(ops[step[0]](x, *step[1:]), dtype=np.float32)
         flags.append(bool(ops["has_nan"](x)) if main else False)
         for step in main:
-            x = np.asarray(ops[step[0]](x, *step[1:]), dtype=np.float32)
+            x = np.asarray(ops[step[0]](x, *step[1:]))
+            if not (step[0] == "hilbert" and np.iscomplexobj(x)):        # hilbert="complex" stays complex64
+                x = x.astype(np.float32, copy=False)
         if rectify:
             x = np.asarray(ops["rectify"](x), dtype=np.float32)
         outs.append(x)
@@ -215,7 +228,9 @@ def _device_run(data, rows, pre, main, rectify):
     nchan, dev = source.nchan, source.dev
     lengths = [b - a for a, b in rows]
     starts = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-    res = torch.empty((int(starts[-1]), nchan), dtype=torch.float32, device=dev)
+    hilbert = steps[-1][1] if steps and steps[-1][0] == "hilbert" else None
+    res = torch.empty((int(starts[-1]), nchan), dtype=torch.complex64 if hilbert == "complex" else torch.float32,
+                      device=dev)
     result = ResultRows(starts, res)
     flags = torch.zeros(len(rows), dtype=torch.int32, device=dev)
     taps_dev = {}
@@ -233,6 +248,8 @@ def _device_run(data, rows, pre, main, rectify):
             in_place_ok = step[0] in ("detrend", "sosfilt", "sosfiltfilt") and (owned or cur is not x)
             if last and final is not None:
                 dst = final
+            elif last and hilbert == "complex":
+                dst = torch.empty((m, n, nchan), dtype=torch.complex64, device=dev)
             elif in_place_ok:
                 dst = cur
             else:
@@ -248,6 +265,8 @@ def _device_run(data, rows, pre, main, rectify):
                 backend.sosfilt(cur, dst, step[1], nan, rect)
             elif step[0] == "sosfiltfilt":
                 backend.sosfiltfilt(cur, dst, step[1], step[2], step[3], nan, rect)
+            elif step[0] == "hilbert":
+                backend.hilbert(cur, dst, step[1], nan)
             else:
                 key = id(step[1])
                 if key not in taps_dev:

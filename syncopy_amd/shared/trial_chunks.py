@@ -16,7 +16,7 @@ import functools
 
 import numpy as np
 
-from ..datatype import AnalogData, device_rows, selected_channels
+from ..datatype import AnalogData, device_rows, require_real_analog, selected_channels
 from .errors import SPYTypeError, SPYValueError
 
 
@@ -25,6 +25,7 @@ def check_analog_input(data):
         raise SPYTypeError(data, varname="data", expected="Syncopy AnalogData object")
     if (data._data is None and data._pending is None) or data.trialdefinition is None:
         raise SPYValueError("non-empty Syncopy data object", varname="data", actual="empty object")
+    require_real_analog(data)
     if data.dimord.index("time") != 0:
         raise SPYValueError("time x channel data", varname="data", actual=f"dimord {data.dimord}")
 
@@ -144,7 +145,8 @@ class TrialSource:
 
 
 class ResultRows:
-    """The stacked (rows, nchan) result tensor `res`, in which output trial k starts at row starts[k]."""
+    """The stacked (rows, nchan) result tensor `res` (of any dtype: the views and copies below are of its dtype), in which
+    output trial k starts at row starts[k]."""
 
     def __init__(self, starts, res):
         self.starts, self.res = starts, res

@@ -8,7 +8,7 @@ import numbers
 
 import numpy as np
 
-from ..datatype import AnalogData, SpectralData, selected_trialdefinition
+from ..datatype import AnalogData, SpectralData, require_real_analog, selected_trialdefinition
 from ..shared.const_def import availableMethods, spectralDTypes
 from ..shared.errors import SPYInfo, SPYTypeError, SPYValueError, SPYWarning
 from ..shared.kwarg_decorators import attached_selection, unwrap_cfg
@@ -50,6 +50,7 @@ def freqanalysis(data, method="mtmfft", output="pow", keeptrials=True, foi=None,
         raise SPYValueError("'float32', 'reference' or 'auto'", varname="precision", actual=str(precision))
     if not isinstance(data, AnalogData) or data.data is None:
         raise SPYTypeError(data, varname="data", expected="non-empty AnalogData")
+    require_real_analog(data)
     classes = {"mtmfft": MultiTaperFFT, "mtmconvol": MultiTaperFFTConvol}
     try:
         from .compRoutines import SuperletTransform, WaveletTransform

@@ -1,0 +1,303 @@
+"""The Hilbert option of spy.preprocessing without a GPU: the route table of csrc/hilbert_route.h, a CPU emulation of the
+three kernel families of csrc/hilbert_kernel.h against the float64 oracle (hilbert_oracle.py) at the shared parity
+criterion, and the front end driven by the NumPy / SciPy model table.
+
+The NaN contract as it is tested here: a non-finite sample is replaced by zero where it is loaded, so the channels
+packed with it come out bit-identical to a run in which that sample IS zero (two real channels share one complex
+transform: no arithmetic could make them independent of the partner's finite values), and within parity of the oracle
+on their own data."""
+import ctypes as C
+import os
+import importlib
+import subprocess
+
+import numpy as np
+import pytest
+import scipy.signal as sps
+
+import hilbert_oracle as HO
+import syncopy_amd as spy
+from parity import assert_parity, excess
+from syncopy_amd.shared.errors import SPYTypeError, SPYValueError
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+pre_mod = importlib.import_module("syncopy_amd.preproc.preprocessing")      # (the package re-exports the function by this name)
+CSRC = os.path.join(HERE, "..", "syncopy_amd", "csrc")
+HOW = dict(compute_method="sequential", routine_classes=HO.HILBERT_OPS)
+KIND = {"abs": 1, "complex": 2, "real": 3, "imag": 4, "angle": 5, "absreal": 6, "absimag": 7}
+COPY, PACKED, BLUE, ANY64 = range(4)
+vp = C.c_void_p
+
+
+def _compile(src, out, headers):
+    deps = [src, os.path.join(HERE, "emu", "hip_emu.h")] + [os.path.join(CSRC, h) for h in headers]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        cxx = "/opt/rocm/lib/llvm/bin/clang++" if os.path.exists("/opt/rocm/lib/llvm/bin/clang++") else "g++"
+        subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-x", "c++", src, "-o", out])
+    return C.CDLL(out)
+
+
+# ---- the route -----------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def route():
+    lib = _compile(os.path.join(HERE, "emu", "hilbert_route_shim.cpp"),
+                   os.path.join(HERE, "emu", "_build", "libhilbertroute.so"), ["hilbert_route.h", "f64_plus_plan.h"])
+    ip = C.POINTER(C.c_int)
+    lib.hilbert_route_query.argtypes = [C.c_longlong, ip, ip, ip, ip, ip, C.POINTER(C.c_longlong), ip, ip, C.c_char_p]
+    lib.hilbert_grid_query.argtypes = [C.c_longlong, C.c_int, C.c_int, ip, ip, ip, C.POINTER(C.c_uint)]
+
+    def query(n):
+        v = [C.c_int() for _ in range(7)]
+        lds = C.c_longlong()
+        text = C.create_string_buffer(256)
+        err = lib.hilbert_route_query(n, v[0], v[1], v[2], v[3], v[4], lds, v[5], v[6], text)
+        keys = ("family", "M", "log2n", "G", "threads", "bluestein", "max_radix")
+        return dict(zip(keys, (x.value for x in v)), err=err, lds=lds.value, text=text.value.decode())
+    query.lib = lib
+    return query
+
+
+@pytest.mark.parametrize("n,family,M,name", [
+    (1, COPY, 1, "hilbert_copy_kernel"),
+    (2, BLUE, 256, "hilbert_packed_kernel<8, 16, Bluestein> N=2"),
+    (15, BLUE, 256, "hilbert_packed_kernel<8, 16, Bluestein> N=15"),
+    (16, PACKED, 16, "hilbert_packed_kernel<4, 64>"),
+    (17, BLUE, 256, "hilbert_packed_kernel<8, 16, Bluestein> N=17"),
+    (128, PACKED, 128, "hilbert_packed_kernel<7, 32>"),
+    (129, BLUE, 512, "hilbert_packed_kernel<9, 8, Bluestein> N=129"),
+    (4095, BLUE, 8192, "hilbert_packed_kernel<13, 1, Bluestein> N=4095"),
+    (4096, PACKED, 4096, "hilbert_packed_kernel<12, 1>"),
+    (4097, ANY64, 16384, "hilbert_any64_kernel N=4097 (Bluestein, M = 16384)"),          # 4097 = 17 x 241
+    (8192, PACKED, 8192, "hilbert_packed_kernel<13, 1>"),
+    (8193, ANY64, 32768, "hilbert_any64_kernel N=8193 (Bluestein, M = 32768)"),          # 8193 = 3 x 2731
+    (4100, ANY64, 4100, "hilbert_any64_kernel N=4100"),                                  # 2^2 5^2 41
+    (16384, ANY64, 16384, "hilbert_any64_kernel N=16384"),
+    (1 << 20, ANY64, 1 << 20, "hilbert_any64_kernel N=1048576"),
+])
+def test_route_table(route, n, family, M, name):
+    r = route(n)
+    assert r["err"] == 0 and (r["family"], r["M"], r["text"]) == (family, M, name)
+    if family in (PACKED, BLUE):
+        assert r["M"] == 1 << r["log2n"] and r["threads"] == r["M"] // 16 * r["G"] and 64 <= r["threads"] <= 512
+        assert r["lds"] <= 160 * 1024 and (family == PACKED or r["M"] >= max(256, 2 * n - 1))
+    if family == ANY64:
+        assert r["threads"] == 256 and r["bluestein"] == ("Bluestein" in name)
+        assert r["max_radix"] <= (4 if r["bluestein"] else 61)
+        assert not r["bluestein"] or r["M"] >= 2 * n - 1
+
+
+def test_route_refuses_beyond_2_pow_20(route):
+    for n in ((1 << 20) + 1, 0, -5):
+        r = route(n)
+        assert r["err"] == -3 and "2^20" in r["text"] and str(1 << 20) in r["text"]
+
+
+def test_route_weights_and_grid(route):
+    for n in (2, 3, 16, 17, 1000, 1001):
+        h = np.zeros(n)
+        h[0] = 1
+        h[1:(n + 1) // 2] = 2
+        if n % 2 == 0:
+            h[n // 2] = 1
+        assert [route.lib.hilbert_weight_query(k, n) for k in range(n)] == list(h)
+    for ntrials, nchan, G in ((1, 1, 1), (3, 65, 16), (125, 256, 1), (7, 1000, 2)):
+        v = [C.c_int() for _ in range(3)]
+        grid = C.c_uint()
+        route.lib.hilbert_grid_query(ntrials, nchan, G, v[0], v[1], v[2], grid)
+        npg, S, ncl = (x.value for x in v)
+        assert npg * G * 4 >= nchan > (npg - 1) * G * 4 and 1 <= S <= max(1, 8 // G) and ncl * S >= npg
+        # every (trial, quad group) is reached by exactly one block of the kernel's XCD map
+        nclt = ntrials * ncl
+        chunk = (nclt + 7) // 8
+        seen = set()
+        for b in range(grid.value):
+            cidx, q = (b & 7) * chunk + (b >> 3) // S, (b >> 3) % S
+            if cidx < nclt and (cidx % ncl) * S + q < npg:
+                seen.add((cidx // ncl, (cidx % ncl) * S + q))
+        assert len(seen) == ntrials * npg
+
+
+# ---- CPU emulation of hilbert_kernel.h -----------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def emu():
+    lib = _compile(os.path.join(HERE, "emu", "hilbert_emu.cpp"), os.path.join(HERE, "emu", "_build", "libhilbertemu.so"),
+                   ["hilbert_kernel.h", "hilbert_route.h", "fft2_device.h", "fft_device.h", "f64_stockham.h",
+                    "f64_plus_plan.h", "cd_math.h", "host_fft.h"])
+    lib.emu_hilbert.argtypes = [vp, vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_char_p]
+
+    def run(x, output):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        out = np.full(x.shape, -7.0, dtype=np.complex64 if output == "complex" else np.float32)
+        flag = np.zeros(x.shape[0], dtype=np.int32)
+        name = C.create_string_buffer(192)
+        rc = lib.emu_hilbert(x.ctypes.data, out.ctypes.data, flag.ctypes.data, *x.shape, KIND[output], name)
+        assert rc == 0, rc
+        return out, flag, name.value.decode()
+    return run
+
+
+def _trials(n, nchan, ntrials=2, seed=0):
+    return (np.random.default_rng(seed + 1000 * n + nchan).normal(size=(ntrials, n, nchan)) + 2.0).astype(np.float32)
+
+
+def _check(got, x, output, what):
+    """parity against the float64 oracle; `angle` as abs(oracle) exp(i angle) against the oracle's analytic signal, so
+    that a phase near the +-pi cut or at a vanishing amplitude is weighed by its amplitude and no element is left out"""
+    if output == "angle":
+        z = HO.analytic64(x)
+        assert got.dtype == np.float32
+        assert_parity(np.abs(z) * np.exp(1j * got.astype(np.float64)), z, what=what)
+    else:
+        ref = HO.hilbert64(x, output)
+        assert got.dtype == (np.complex64 if output == "complex" else np.float32)
+        assert_parity(got, ref, what=what)
+    if output == "real":
+        assert np.array_equal(got, x)          # the real part of the analytic signal is the input itself
+
+
+# PACKED: closing radix 1 (16, 256, 4096), 2 (32, 512), 4 (64), 8 (128, 2048); BLUE: Nyquist weight present (2, 1000)
+# and absent (3, 17, 129, 1001); ANY64: 4097 in Bluestein's form, 4100 in radix form (largest factor 41)
+EMU_LENGTHS = {PACKED: (16, 32, 64, 128, 256, 512, 2048, 4096), BLUE: (2, 3, 17, 129, 1000, 1001), ANY64: (4097, 4100)}
+
+
+@pytest.mark.parametrize("n", [n for fam in (PACKED, BLUE, ANY64) for n in EMU_LENGTHS[fam]] + [1])
+def test_emu_lengths(emu, route, n):
+    x = _trials(n, 5)
+    got, flag, name = emu(x, "complex")
+    assert name == route(n)["text"] and not flag.any()
+    _check(got, x, "complex", f"N={n}")
+    print(f"N={n} {name}: excess {excess(got, HO.hilbert64(x, 'complex')):.3f}")
+
+
+def test_emu_two_samples(emu):
+    """h = [1, 1]: the analytic signal of two samples is the samples, H[x] = 0 (too small a reference for `imag` alone)"""
+    x = _trials(2, 3)
+    got, _, name = emu(x, "complex")
+    assert "Bluestein" in name and np.array_equal(got.real, x)
+    assert np.abs(got.imag).max() <= 1e-6 * np.abs(x).max()
+
+
+@pytest.mark.parametrize("n,nchans", [(256, (1, 3, 4, 63, 65)), (1000, (1, 3, 4, 7, 9)), (4100, (1, 4))])
+def test_emu_channel_counts(emu, route, n, nchans):
+    """1, 3, 4 channels and 4G - 1, 4G + 1 (G quads per workgroup: a last quad group that is nearly empty or full)"""
+    G = route(n)["G"]
+    assert n == 4100 or {4 * G - 1, 4 * G + 1} <= set(nchans)
+    for nchan in nchans:
+        x = _trials(n, nchan)
+        for output in ("complex", "imag"):
+            got, flag, _ = emu(x, output)
+            assert not flag.any()
+            _check(got, x, output, f"N={n}, {nchan} channels, {output}")
+
+
+@pytest.mark.parametrize("n", [256, 1000, 4100, 1])
+@pytest.mark.parametrize("output", HO.OUTPUTS)
+def test_emu_outputs(emu, n, output):
+    x = _trials(n, 5)
+    got, _, _ = emu(x, output)
+    _check(got, x, output, f"N={n}, {output}")
+
+
+@pytest.mark.parametrize("n,bad", [(256, np.nan), (1000, np.inf), (4097, -np.inf), (4100, np.nan), (1, np.nan)])
+def test_emu_nan_contract(emu, n, bad):
+    nchan = 6                                  # channel 1 shares a packed transform with 3 (quads) / with 0 (pairs)
+    x = _trials(n, nchan, ntrials=3)
+    dirty, zeroed = x.copy(), x.copy()
+    dirty[1, n // 3, 1] = bad
+    zeroed[1, n // 3, 1] = 0.0
+    for output in ("complex", "abs"):
+        got, flag, _ = emu(dirty, output)
+        ref, flag0, _ = emu(zeroed, output)
+        assert list(flag) == [0, 1, 0] and not flag0.any()
+        assert np.isnan(got[1, :, 1]).all()
+        keep = np.ones(got.shape, dtype=bool)
+        keep[1, :, 1] = False
+        assert not np.isnan(got[keep]).any()
+        assert np.array_equal(got[keep].view(np.uint32), ref[keep].view(np.uint32))       # bit-identical partners
+        others = [c for c in range(nchan) if c != 1]
+        _check(got[:, :, others], x[:, :, others], output, f"N={n}, partners of the {bad} channel")
+
+
+# ---- the front end with the model table ------------------------------------------------------------------------------
+def _data(lengths=(300, 200, 300), nchan=4, seed=0):
+    rng = np.random.default_rng(seed)
+    x = (rng.normal(size=(sum(lengths), nchan)) + 2.0).astype(np.float32)
+    e = np.concatenate([[0], np.cumsum(lengths)])
+    return spy.AnalogData(x, samplerate=1000.0, trialdefinition=np.stack([e[:-1], e[1:], np.zeros(len(lengths))], 1))
+
+
+def test_hilbert_is_served():
+    """the test that shows the feature: NotImplementedError before the Hilbert step existed"""
+    data = _data()
+    out = spy.preprocessing(data, filter_class=None, polyremoval=0, hilbert="abs", **HOW)
+    assert out.data.dtype == np.float32 and out.data.shape == data.data.shape
+    for g, x in zip(out.trials, data.trials):
+        d = sps.detrend(x, type="constant", axis=0)
+        assert_parity(g, np.abs(sps.hilbert(d.astype(np.float64), axis=0)), what="abs")
+
+
+@pytest.mark.parametrize("output", HO.OUTPUTS)
+def test_front_end_dtype_shape_and_cfg(output):
+    data = _data()
+    data.cfg = {"earlier": {"a": 1}}
+    out = spy.preprocessing(data, filter_class=None, polyremoval=1, hilbert=output, **HOW)
+    assert out.data.dtype == (np.complex64 if output == "complex" else np.float32)
+    assert out.data.shape == data.data.shape and out.dimord == data.dimord and out.samplerate == data.samplerate
+    assert list(out.channel) == list(data.channel) and np.array_equal(out.trialdefinition, data.trialdefinition)
+    assert out.cfg["preprocessing"]["hilbert"] == output and out.cfg["earlier"] == {"a": 1}
+    assert out.info["nan_trials"] == []
+    for g, x in zip(out.trials, data.trials):            # unequal trial lengths: circular over each trial's own length
+        assert np.array_equal(g, HO.hilbert(HO.PREPROC_OPS["detrend"](x, 1), output))
+
+
+def test_front_end_chain_selection_and_nan():
+    data = _data()
+    data.data[300 + 57, 2] = np.nan
+    sel = {"trials": [2, 1], "channel": [3, 2]}
+    with pytest.warns(UserWarning, match="NaN"):
+        out = spy.preprocessing(data, filter_type="bp", freq=[20, 80], hilbert="abs", select=sel, **HOW)
+    assert data.selection is None and out.info["nan_trials"] == [1] and list(out.channel) == list(data.channel[[3, 2]])
+    assert out.data.shape == (500, 2) and out.data.dtype == np.float32
+    sos = sps.butter(4, [20, 80], "bp", fs=1000.0, output="sos")
+    band = sps.sosfiltfilt(sos, data.trials[2][:, [3, 2]], axis=0).astype(np.float32)
+    assert np.array_equal(out.trials[0], np.abs(sps.hilbert(band.astype(np.float64), axis=0)).astype(np.float32))
+    assert np.isnan(out.trials[1][:, 1]).all() and not np.isnan(out.trials[1][:, 0]).any()
+    z = spy.preprocessing(data, filter_class=None, zscore=True, hilbert="angle", select={"trials": [0]}, **HOW)
+    assert np.array_equal(z.data, HO.hilbert(HO.PREPROC_OPS["standardize"](data.trials[0]), "angle"))
+
+
+def test_front_end_refusals(monkeypatch):
+    data = _data()
+    with pytest.raises(SPYValueError):
+        spy.preprocessing(data, freq=10, rectify=True, hilbert="abs", **HOW)
+    with pytest.raises(SPYValueError):
+        spy.preprocessing(data, freq=10, hilbert="phase", **HOW)
+    with pytest.raises(SPYValueError):
+        spy.preprocessing(data, filter_class=None, hilbert="abs", **HOW)       # the reference asks for a method too
+    with pytest.raises(NotImplementedError):                                    # a table without the routine says so
+        spy.preprocessing(data, freq=10, hilbert="abs", compute_method="sequential",
+                          routine_classes=HO.PREPROC_OPS)
+    # a trial beyond 2^20 samples is refused from the trial definition, ahead of any upload or device call
+    assert pre_mod.MAX_HILBERT_SAMPLES == 1 << 20
+    monkeypatch.setattr(pre_mod, "MAX_HILBERT_SAMPLES", 299)
+    with pytest.raises(SPYValueError, match="Hilbert"):
+        spy.preprocessing(data, filter_class=None, polyremoval=0, hilbert="abs")
+    monkeypatch.setattr(pre_mod, "MAX_HILBERT_SAMPLES", 300)
+    spy.preprocessing(data, filter_class=None, polyremoval=0, hilbert="abs", **HOW)
+
+
+def test_complex_result_is_refused_by_the_other_front_ends():
+    z = spy.preprocessing(_data(), filter_class=None, polyremoval=0, hilbert="complex", **HOW)
+    assert z.data.dtype == np.complex64
+    for call in (lambda: spy.freqanalysis(z, method="mtmfft"),
+                 lambda: spy.connectivityanalysis(z, method="coh"),
+                 lambda: spy.resampledata(z, resamplefs=500.0),
+                 lambda: spy.timelockanalysis(z),
+                 lambda: spy.preprocessing(z, filter_class=None, polyremoval=0),
+                 lambda: spy.preprocessing(z, filter_class=None, polyremoval=0, **HOW)):
+        with pytest.raises(SPYTypeError):
+            call()
+    real = spy.preprocessing(_data(), filter_class=None, polyremoval=0, hilbert="abs", **HOW)
+    again = spy.preprocessing(real, filter_class=None, polyremoval=0, **HOW)   # a real result goes on as before
+    assert again.data.dtype == np.float32
