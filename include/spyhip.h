@@ -537,6 +537,52 @@ const char* spyhip_hilbert_plan_kernel_name(const spyhip_hilbert_plan* plan);
 int spyhip_cov_f32(spyhip_ctx* ctx, const float* x_d, float* out_d, int64_t ntrials, int64_t n, int64_t nchan,
                    int64_t ddof);
 
+/* ---- spy.spike_psth (statistics/spike_psth.py; statistics/psth.py: psth, get_chan_unit_combs; statistics/
+ * compRoutines.py: psth_cF, PSTH).  The spike table lives on the device as three arrays of one entry per spike, SORTED
+ * BY SAMPLE: sample_d int64, chan_d int32, unit_d int32 (16 bytes per spike).  Trial t owns the rows [row_lo_d[t],
+ * row_hi_d[t]) (np.searchsorted(sample, [start, end]), datatype/discrete_data.py:186-196; a repeated trial names its
+ * rows again) and puts a spike at time = (double)(sample - start_d[t] + onset_d[t]) / samplerate, one IEEE float64
+ * division (psth.py: _calc_time).  A spike counts in bin b when edges[b] <= time < edges[b + 1], the last bin also
+ * takes time == edges[nbins] (np.histogram2d with explicit edges); edges_d holds nedges = nbins + 1 float64 values as
+ * the host computed them.  Counts are integer sums in LDS: every result is bitwise reproducible, and spikecount and
+ * rate are the reference's bits.  No entry point allocates, synchronises, or uses a global atomic; all run on the
+ * context's stream.  channel < nchan and unit < nunit for every row of a trial (rows that break this are ignored),
+ * nchan * nunit <= 2^24, ntrials < 2^31.
+ * DEVIATION, on purpose: a spike on channel c, unit u counts in column (c, u).  The reference hands raw channel numbers
+ * to histogram2d with the channel bins arange(k + 1), k = distinct channels of the trial, and miscounts whenever a
+ * trial's channels are not exactly 0 .. k-1. */
+/* get_chan_unit_combs without the per-trial np.unique loop: flags_d[c * nunit + u] = 1 (uint8, zeroed by the caller)
+ * for every row of the trials whose channel c has chan_ok_d[c] != 0 and whose unit u has unit_ok_d[u] != 0 (uint8
+ * masks of nchan and nunit entries: the selection).  max_rows = the longest trial, which sizes the grid. */
+int spyhip_psth_presence(spyhip_ctx* ctx, const int32_t* chan_d, const int32_t* unit_d, const int64_t* row_lo_d,
+                         const int64_t* row_hi_d, int64_t ntrials, int64_t max_rows, const uint8_t* chan_ok_d,
+                         int64_t nchan, const uint8_t* unit_ok_d, int64_t nunit, uint8_t* flags_d);
+/* rows_d (ntrials, nedges) int64: rows_d[t][e] = the first row of trial t with time >= edges_d[e], for the last edge
+ * with time > edges_d[e] (row_hi_d[t] when there is none): the spikes of (t, bin b) are rows [rows_d[t][b],
+ * rows_d[t][b + 1]).  A binary search per (trial, edge). */
+int spyhip_psth_bin_rows(spyhip_ctx* ctx, const int64_t* sample_d, const int64_t* row_lo_d, const int64_t* row_hi_d,
+                         const int64_t* start_d, const int64_t* onset_d, int64_t ntrials, const double* edges_d,
+                         int64_t nedges, double samplerate, int64_t* rows_d);
+/* out_d (ntrials, nbins, ncols) float32, every element written once: NaN for the bins outside [lohi_d[2 t],
+ * lohi_d[2 t + 1]) (int32 pairs: the mask of psth.py:133-155, worked out by the host), else (float)(count * scale) with
+ * the product in float64: scale = 1 for "spikecount" (and ahead of spyhip_psth_proportion), 1 / np.diff(edges)[0] for
+ * "rate".  lut_d[c * nunit + u] (int32) = the column of (c, u), or -1 for a pair that is not selected. */
+int spyhip_psth_count(spyhip_ctx* ctx, const int32_t* chan_d, const int32_t* unit_d, const int64_t* rows_d,
+                      const int32_t* lut_d, int64_t nchan, int64_t nunit, const int32_t* lohi_d, int64_t ntrials,
+                      int64_t nbins, int64_t ncols, double scale, float* out_d);
+/* output = "proportion", in place on the out_d of spyhip_psth_count(scale = 1).  Per trial and column (c, u), in
+ * float64: v[b] = count[b] / (edges[b + 1] - edges[b]) / S, S = the trial's selected spikes of unit u with edges[0] <=
+ * time <= edges[nbins] (histogram2d's density=True; 0 / 0 = NaN when the unit occurs in the trial but not in the
+ * window), v = 0 for a unit that does not occur in the trial; NaN where the count is masked; then v[b] / nansum_b v[b]
+ * with a sum of 0 replaced by 1, the sum taken in bin order, and one rounding to float32.  unit_k_d[u] (int32, nunit
+ * entries) = dense index < nk of a unit that has a column, col_k_d[column] (int32) = the dense index of its unit; s_d =
+ * ntrials * nk int32 of work space (S, or -1 for an absent unit, on return). */
+int spyhip_psth_proportion(spyhip_ctx* ctx, const int32_t* chan_d, const int32_t* unit_d, const int64_t* row_lo_d,
+                           const int64_t* row_hi_d, const int64_t* rows_d, const int32_t* lut_d, int64_t nchan,
+                           int64_t nunit, const int32_t* unit_k_d, const int32_t* col_k_d, int64_t nk,
+                           const double* edges_d, int64_t ntrials, int64_t nbins, int64_t ncols, int32_t* s_d,
+                           float* out_d);
+
 #ifdef __cplusplus
 }
 #endif

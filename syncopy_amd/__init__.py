@@ -9,7 +9,7 @@ All arithmetic runs in libspyhip.so (hand-written HIP for gfx950); there is no C
 """
 __version__ = "0.1.0"
 
-from .datatype import AnalogData, CrossSpectralData, SpectralData, TimeLockData  # noqa: F401
+from .datatype import AnalogData, CrossSpectralData, SpectralData, SpikeData, TimeLockData  # noqa: F401
 from . import synthdata  # noqa: F401
 from .io import load, save  # noqa: F401
 from .shared.kwarg_decorators import StructDict, get_defaults  # noqa: F401
@@ -20,7 +20,7 @@ _LAZY = {"freqanalysis": ".specest.freqanalysis", "connectivityanalysis": ".conn
          "mean": ".statistics.summary_stats", "var": ".statistics.summary_stats", "std": ".statistics.summary_stats",
          "median": ".statistics.summary_stats", "itc": ".statistics.summary_stats",
          "preprocessing": ".preproc.preprocessing", "resampledata": ".preproc.resampledata",
-         "timelockanalysis": ".statistics.timelockanalysis"}
+         "timelockanalysis": ".statistics.timelockanalysis", "spike_psth": ".statistics.spike_psth"}
 
 
 def release_device_buffers():

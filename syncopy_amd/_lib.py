@@ -116,6 +116,12 @@ SIGNATURES = {
     "spyhip_hilbert_plan_destroy": (C.c_int, [vp]),
     "spyhip_hilbert_plan_kernel_name": (C.c_char_p, [vp]),
     "spyhip_cov_f32": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "spyhip_psth_presence": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp]),
+    "spyhip_psth_bin_rows": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_double, vp]),
+    "spyhip_psth_count": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int64,
+                                    C.c_double, vp]),
+    "spyhip_psth_proportion": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp,
+                                         C.c_int64, C.c_int64, C.c_int64, vp, vp]),
 }
 
 

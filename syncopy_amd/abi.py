@@ -231,6 +231,84 @@ class Device:
             xd.free()
             out.free()
 
+    # ---- spy.spike_psth
+    def _put(self, arr, dtype):
+        arr = np.ascontiguousarray(arr, dtype=dtype)
+        buf = Buffer(self, arr.shape, dtype)
+        if arr.nbytes:
+            check(self.lib.spyhip_upload(self.handle, buf.ptr, arr.ctypes.data_as(C.c_void_p), arr.nbytes),
+                  "spyhip_upload")
+        return buf
+
+    def psth(self, spikes, trialdefinition, samplerate, edges, output="rate", channels=None, units=None):
+        """Peristimulus time histograms (psth_cF for every trial): `spikes` (nSpikes, 3) integers [sample, channel, unit]
+        sorted by sample, `trialdefinition` (T, 3) [start, end, onset] in samples, `edges` the float64 bin edges in
+        seconds, `output` 'rate', 'spikecount' or 'proportion'; `channels` / `units`: the channel / unit numbers to keep
+        (None: all).  Returns (hist (T, nbins, ncols) float32, columns (ncols, 2) int64): one column per (channel, unit)
+        pair that occurs in the trials, sorted; NaN in the bins a trial does not reach (psth.py:133-155)."""
+        from .statistics.spike_psth import column_tables, valid_bins
+        spikes = np.asarray(spikes)
+        trl = np.asarray(trialdefinition, dtype=np.float64)
+        edges = np.ascontiguousarray(edges, dtype=np.float64)
+        if spikes.ndim != 2 or spikes.shape[1] != 3 or trl.ndim != 2 or trl.shape[1] < 3 or edges.ndim != 1:
+            raise ValueError("spikes must be (nSpikes, 3), trialdefinition (T, 3), edges one-dimensional")
+        if output not in ("rate", "spikecount", "proportion") or edges.size < 2:
+            raise ValueError("output is 'rate', 'spikecount' or 'proportion'; at least two edges")
+        sample = np.ascontiguousarray(spikes[:, 0], dtype=np.int64)
+        if spikes.shape[0] < 1 or np.any(np.diff(sample) < 0) or spikes[:, 1:].min() < 0 or spikes[:, 1:].max() >= 2 ** 31:
+            raise ValueError("spikes sorted by sample, channel and unit numbers in [0, 2^31)")
+        nchan, nunit = int(spikes[:, 1].max()) + 1, int(spikes[:, 2].max()) + 1
+        chan_ok, unit_ok = np.zeros(nchan, np.uint8), np.zeros(nunit, np.uint8)
+        chan_ok[slice(None) if channels is None else np.asarray(channels, dtype=np.int64)] = 1
+        unit_ok[slice(None) if units is None else np.asarray(units, dtype=np.int64)] = 1
+        T, nbins = trl.shape[0], edges.size - 1
+        rows = np.searchsorted(sample, trl[:, :2].astype(np.int64).ravel()).reshape(T, 2).astype(np.int64)
+        rows[:, 1] = np.maximum(rows[:, 1], rows[:, 0])
+        lohi = np.array([valid_bins(edges, s, e, o, float(samplerate)) for s, e, o in trl[:, :3]],
+                        dtype=np.int32).reshape(T, 2)
+        bufs = []
+
+        def put(arr, dtype):
+            bufs.append(self._put(arr, dtype))
+            return bufs[-1]
+        try:
+            sample_d, chan_d, unit_d = put(sample, np.int64), put(spikes[:, 1], np.int32), put(spikes[:, 2], np.int32)
+            lo_d, hi_d = put(rows[:, 0], np.int64), put(rows[:, 1], np.int64)
+            flags_d = Buffer(self, (nchan, nunit), np.uint8, zero=True)
+            bufs.append(flags_d)
+            check(self.lib.spyhip_psth_presence(self.handle, chan_d.ptr, unit_d.ptr, lo_d.ptr, hi_d.ptr, T,
+                                                int((rows[:, 1] - rows[:, 0]).max(initial=0)), put(chan_ok, np.uint8).ptr,
+                                                nchan, put(unit_ok, np.uint8).ptr, nunit, flags_d.ptr),
+                  "spyhip_psth_presence")
+            columns, lut, unit_k, col_k, nk = column_tables(flags_d.numpy())
+            ncols = columns.shape[0]
+            if ncols == 0 or T == 0:
+                return np.zeros((T, nbins, ncols), dtype=np.float32), columns
+            rows_d = Buffer(self, (T, nbins + 1), np.int64)
+            out = Buffer(self, (T, nbins, ncols), np.float32)
+            bufs += [rows_d, out]
+            edges_d, lut_d = put(edges, np.float64), put(lut, np.int32)
+            check(self.lib.spyhip_psth_bin_rows(self.handle, sample_d.ptr, lo_d.ptr, hi_d.ptr,
+                                                put(trl[:, 0], np.int64).ptr, put(trl[:, 2], np.int64).ptr, T,
+                                                edges_d.ptr, nbins + 1, float(samplerate), rows_d.ptr),
+                  "spyhip_psth_bin_rows")
+            scale = float(1 / np.diff(edges)[0]) if output == "rate" else 1.0
+            check(self.lib.spyhip_psth_count(self.handle, chan_d.ptr, unit_d.ptr, rows_d.ptr, lut_d.ptr, nchan, nunit,
+                                             put(lohi, np.int32).ptr, T, nbins, ncols, scale, out.ptr),
+                  "spyhip_psth_count")
+            if output == "proportion":
+                work = Buffer(self, (T, nk), np.int32)
+                bufs.append(work)
+                check(self.lib.spyhip_psth_proportion(self.handle, chan_d.ptr, unit_d.ptr, lo_d.ptr, hi_d.ptr, rows_d.ptr,
+                                                      lut_d.ptr, nchan, nunit, put(unit_k, np.int32).ptr,
+                                                      put(col_k, np.int32).ptr, nk, edges_d.ptr, T, nbins, ncols,
+                                                      work.ptr, out.ptr), "spyhip_psth_proportion")
+            return out.numpy(), columns
+        finally:
+            self.synchronize()
+            for b in bufs:
+                b.free()
+
     def close(self):
         if self.handle is not None:
             self.lib.spyhip_ctx_destroy(self.handle)

@@ -1378,3 +1378,81 @@ def cov(x, ddof=None, out=None):
     check(ctx.lib.spyhip_cov_f32(ctx.handle, _ptr(x), _ptr(out), T, n, nchan, 1 if ddof is None else int(ddof)),
           "spyhip_cov_f32")
     return out
+
+
+# ---- spy.spike_psth (csrc/psth.hip) --------------------------------------------------------------------------------
+def _psth_table(chan, unit):
+    assert chan.is_cuda and chan.dtype == torch.int32 and chan.is_contiguous() and chan.dim() == 1
+    assert unit.is_cuda and unit.dtype == torch.int32 and unit.is_contiguous() and unit.shape == chan.shape
+
+
+def _psth_i64(*ts):
+    n = ts[0].numel()
+    for t in ts:
+        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 1 and t.numel() == n
+    return n
+
+
+def psth_presence(chan, unit, row_lo, row_hi, max_rows, chan_ok, unit_ok):
+    """flags (nchan * nunit) uint8: 1 where a spike of channel c, unit u with chan_ok[c] and unit_ok[u] (uint8 masks) lies
+    in one of the row ranges [row_lo[t], row_hi[t]) of the table (chan, unit: int32, one entry per spike)"""
+    _psth_table(chan, unit)
+    T = _psth_i64(row_lo, row_hi)
+    for m in (chan_ok, unit_ok):
+        assert m.is_cuda and m.dtype == torch.uint8 and m.is_contiguous() and m.dim() == 1
+    nchan, nunit = int(chan_ok.numel()), int(unit_ok.numel())
+    flags = torch.zeros(nchan * nunit, dtype=torch.uint8, device=chan.device)
+    ctx = _stat_ctx(chan)
+    check(ctx.lib.spyhip_psth_presence(ctx.handle, _ptr(chan), _ptr(unit), _ptr(row_lo), _ptr(row_hi), T, int(max_rows),
+                                       _ptr(chan_ok), nchan, _ptr(unit_ok), nunit, _ptr(flags)), "spyhip_psth_presence")
+    return flags
+
+
+def psth_bin_rows(sample, row_lo, row_hi, start, onset, edges, samplerate):
+    """rows (T, nedges) int64: the first row of trial t whose time (sample - start[t] + onset[t]) / samplerate is >=
+    edges[e] (> for the last edge) inside [row_lo[t], row_hi[t]); sample: int64, sorted; edges: float64"""
+    assert sample.is_cuda and sample.dtype == torch.int64 and sample.is_contiguous() and sample.dim() == 1
+    T = _psth_i64(row_lo, row_hi, start, onset)
+    assert edges.is_cuda and edges.dtype == torch.float64 and edges.is_contiguous() and edges.dim() == 1
+    rows = torch.empty((T, edges.numel()), dtype=torch.int64, device=sample.device)
+    ctx = _stat_ctx(sample)
+    check(ctx.lib.spyhip_psth_bin_rows(ctx.handle, _ptr(sample), _ptr(row_lo), _ptr(row_hi), _ptr(start), _ptr(onset), T,
+                                       _ptr(edges), int(edges.numel()), float(samplerate), _ptr(rows)),
+          "spyhip_psth_bin_rows")
+    return rows
+
+
+def psth_count(chan, unit, rows, lut, nchan, nunit, lohi, ncols, scale):
+    """(T, nbins, ncols) float32: (float)(count * scale) of the spikes in rows [rows[t][b], rows[t][b + 1]) per column
+    lut[channel * nunit + unit] (int32, -1: not selected), NaN outside the trial's bins [lohi[t][0], lohi[t][1])"""
+    _psth_table(chan, unit)
+    assert rows.is_cuda and rows.dtype == torch.int64 and rows.is_contiguous() and rows.dim() == 2
+    T, nbins = int(rows.shape[0]), int(rows.shape[1]) - 1
+    assert lut.is_cuda and lut.dtype == torch.int32 and lut.is_contiguous() and lut.numel() == nchan * nunit
+    assert lohi.is_cuda and lohi.dtype == torch.int32 and lohi.is_contiguous() and tuple(lohi.shape) == (T, 2)
+    out = torch.empty((T, nbins, int(ncols)), dtype=torch.float32, device=chan.device)
+    ctx = _stat_ctx(chan)
+    check(ctx.lib.spyhip_psth_count(ctx.handle, _ptr(chan), _ptr(unit), _ptr(rows), _ptr(lut), int(nchan), int(nunit),
+                                    _ptr(lohi), T, nbins, int(ncols), float(scale), _ptr(out)), "spyhip_psth_count")
+    return out
+
+
+def psth_proportion(chan, unit, row_lo, row_hi, rows, lut, nchan, nunit, unit_k, col_k, nk, edges, out):
+    """output "proportion" in place on the counts `out` of psth_count(scale=1): per column count / bin width / (the
+    trial's spikes of the column's unit inside the window), over its nansum along the bins (0 -> 1), in float64.
+    unit_k[unit] / col_k[column]: int32 dense index (< nk) of the units that have a column."""
+    _psth_table(chan, unit)
+    T = _psth_i64(row_lo, row_hi)
+    nbins, ncols = int(out.shape[1]), int(out.shape[2])
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] == T
+    assert rows.dtype == torch.int64 and rows.is_contiguous() and tuple(rows.shape) == (T, nbins + 1)
+    assert lut.dtype == torch.int32 and lut.is_contiguous() and lut.numel() == nchan * nunit
+    assert unit_k.is_cuda and unit_k.dtype == torch.int32 and unit_k.is_contiguous() and unit_k.numel() == nunit
+    assert col_k.is_cuda and col_k.dtype == torch.int32 and col_k.is_contiguous() and col_k.numel() == ncols
+    assert edges.dtype == torch.float64 and edges.is_contiguous() and edges.numel() == nbins + 1
+    work = torch.empty((T, int(nk)), dtype=torch.int32, device=chan.device)
+    ctx = _stat_ctx(chan)
+    check(ctx.lib.spyhip_psth_proportion(ctx.handle, _ptr(chan), _ptr(unit), _ptr(row_lo), _ptr(row_hi), _ptr(rows),
+                                         _ptr(lut), int(nchan), int(nunit), _ptr(unit_k), _ptr(col_k), int(nk),
+                                         _ptr(edges), T, nbins, ncols, _ptr(work), _ptr(out)), "spyhip_psth_proportion")
+    return out

@@ -408,3 +408,6 @@ def selected_channel_labels(data):
 
 def selected_trialdefinition(data):
     return data.trialdefinition.copy() if data.selection is None else data.selection.trialdefinition.copy()
+
+
+from .spike_data import SpikeData, SpikeSelection  # noqa: E402,F401  (needs _Base, hence down here)

@@ -1,9 +1,10 @@
 """Synthetic AnalogData generators with the reference's sampling scheme
 (syncopy/synthdata/analog.py:20-48,186-252 and the per-trial seeding of
-syncopy/synthdata/utils.py:53-55), used for parity fixtures and the benchmark inputs."""
+syncopy/synthdata/utils.py:53-55), used for parity fixtures and the benchmark inputs; `poisson_noise` is the SpikeData
+generator of syncopy/synthdata/spikes.py."""
 import numpy as np
 
-from .datatype import AnalogData
+from .datatype import AnalogData, SpikeData
 
 
 def _trial_seeds(seed, nTrials):
@@ -67,3 +68,33 @@ def ar2_uncoupled_fast(nChannels, nSamples, nTrials, alphas=(0.55, -0.8), seed=0
     for i in range(2, nSamples):
         x[:, i] = a1 * x[:, i - 1] + a2 * x[:, i - 2] + torch.randn((nTrials, nChannels), generator=g, device=dev)
     return x.reshape(nTrials * nSamples, nChannels)
+
+
+def poisson_noise(nTrials=10, nSpikes=10000, nChannels=3, nUnits=10, intensity=0.1, samplerate=10000, seed=None):
+    """Poisson (shot) noise as SpikeData: `nSpikes` spikes over all trials at `intensity` spikes per sample, so a trial is
+    about nSpikes / (intensity * nTrials) samples long.  Trials are shortened by up to 10 % of that, the trigger offsets
+    lie between 5 % and 20 % of the shortest trial before its start, and channels and units get uniformly random
+    weights.  Signature, order of the draws from default_rng(seed) and hence spikes and trial definition for a seed are
+    those of syncopy/synthdata/spikes.py: poisson_noise."""
+    def get_rdm_weights(size):
+        pvec = np.random.default_rng(seed).uniform(size=size)
+        return pvec / pvec.sum()
+
+    rng = np.random.default_rng(seed)
+    T_max = int(nSpikes / intensity)                    # total length of all trials combined
+    # (choice over the integer T_max draws what choice over range(T_max) draws, without building the list)
+    spike_samples = np.sort(rng.choice(T_max, size=nSpikes, replace=False))
+    channels = rng.choice(np.arange(nChannels), p=get_rdm_weights(nChannels), size=nSpikes, replace=True)
+    units = rng.choice(np.arange(nUnits), p=get_rdm_weights(nUnits), size=nSpikes, replace=True)
+
+    step = T_max // nTrials
+    trl_intervals = np.arange(T_max + 1, step=step)
+    idx_start = trl_intervals[:-1]
+    idx_end = trl_intervals[1:] - 1
+    idx_end = idx_end - np.r_[rng.integers(step // 10, size=nTrials - 1), 0]
+    shortest_trial = np.min(idx_end - idx_start)
+    idx_offset = -rng.choice(np.arange(0.05 * shortest_trial, 0.2 * shortest_trial, dtype=int), size=nTrials,
+                             replace=True)
+    trldef = np.vstack([idx_start, idx_end, idx_offset]).T
+    data = np.vstack([spike_samples, channels, units]).T
+    return SpikeData(data=data, trialdefinition=trldef, dimord=["sample", "channel", "unit"], samplerate=samplerate)
