@@ -130,7 +130,8 @@ __global__ void __launch_bounds__(256) jack_coh_kernel(JackArgs a) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float lx = (T * Sij[q].x - s[q].x * invK) * invT1;
-            const float ly = (T * Sij[q].y - s[q].y * invK) * invT1;
+            // (x_i conj(x_i) is real; its FMA chain leaves a rounding residue in the imaginary part)
+            const float ly = (bi == bj && ti == tq * 4 + q) ? 0.f : (T * Sij[q].y - s[q].y * invK) * invT1;
             const float ljj = (T * Sjj[q] - pj[q] * invK) * invT1;
             const float rden = fast_rsqrt(lii * ljj);                // 1 ulp: d_t itself is good to ~1e-7 |c| only
             const float2 c = make_float2(lx * rden, ly * rden);
@@ -152,6 +153,10 @@ __global__ void __launch_bounds__(256) jack_coh_kernel(JackArgs a) {
     for (int q = 0; q < 4; ++q) {
         const int j = bj * 32 + tq * 4 + q;
         if (j >= a.C) continue;
+        // a diagonal tile evaluates both (i, j) and (j, i), and the two FMA chains of x_i conj(x_j) and x_j conj(x_i)
+        // round differently in the last bit: only the lower triangle is stored and mirrored there too, so that the
+        // sums are exactly Hermitian / symmetric like the reference's
+        if (bi == bj && j > i) continue;
         const size_t o = fb + (size_t)i * a.C + j;
         if (CPLX) {
             a.sum_d[2 * o] += sd[q];
@@ -160,7 +165,7 @@ __global__ void __launch_bounds__(256) jack_coh_kernel(JackArgs a) {
             a.sum_d[o] += sd[q];
         }
         a.sum_d2[o] += sd2[q];
-        if (bi == bj) continue;                          // diagonal tiles hold both triangles themselves
+        if (i == j) continue;
         // mirror (j, i): the coherency is Hermitian - imaginary part and phase change sign, the rest is symmetric
         const size_t m = fb + (size_t)j * a.C + i;
         if (CPLX) {

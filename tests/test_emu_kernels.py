@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import emu_driver as E
+import jack_oracle as JO
 from oracle import spy_oracle as O
 from parity import assert_parity, excess
 from cwt64_ref import assert_cwt64, cwt64_ref as _cwt64_ref
@@ -253,19 +254,23 @@ def test_csd_recut_tail(C, F, R, force_4m, code):
     np.testing.assert_array_equal(acc[:-1], whole[:-1])          # the frequencies of the main launch: the same kernel
 
 
-@pytest.mark.parametrize("C,F,T,K", [(5, 4, 6, 3), (40, 2, 7, 1), (70, 1, 5, 7)])
+@pytest.mark.parametrize("C,F,T,K", [(5, 4, 6, 3), (40, 2, 7, 1), (70, 1, 5, 7)] + JO.PPC_EDGE_CASES)
 def test_ppc_kernel(C, F, T, K):
-    """K7's kernel source on the CPU: phasor sums + closed form = the oracle's walk over all trial pairs."""
+    """K7's kernel source on the CPU: phasor sums + closed form = the oracle's walk over all trial pairs.  The shapes
+    of jack_oracle.PPC_EDGE_CASES: more than 16 tapers (the generic staging walk), tile edges, four tile rows,
+    frequencies around the 8-XCD mapping, a first launch of one trial."""
     rng = np.random.default_rng(C)
     spec = (rng.normal(size=(T, K, F, C)) + 1j * rng.normal(size=(T, K, F, C))).astype(np.complex64)
     spec += (2.0 * rng.normal(size=(1, K, F, C))).astype(np.complex64)
     spec[..., C - 1] = 0                                # np.angle(0) = 0: consistent with everything
     st = O.spectral_dyadic_product(spec)
     ref = O.ppc(st)[0]
+    first = 1 if (C, F, T, K) in JO.PPC_EDGE_CASES else 2
     U = np.zeros((F, C, C), np.complex64)
-    E.ppc_accumulate(spec[:2].reshape(-1, F, C), K, U)
-    E.ppc_accumulate(spec[2:].reshape(-1, F, C), K, U)
+    E.ppc_accumulate(spec[:first].reshape(-1, F, C), K, U)
+    E.ppc_accumulate(spec[first:].reshape(-1, F, C), K, U)
     got = E.ppc_finalize(U, T, True)
+    print(f"ppc {C}-{F}-{T}-{K}: err/tol {excess(got, ref, rtol=1e-4, atol_rel=2e-5):.3f}")
     assert_parity(got, ref, what="ppc", rtol=1e-4, atol_rel=2e-5)
     assert np.array_equal(got, got.transpose(0, 2, 1)) and np.allclose(got[:, C - 1], 1, atol=1e-6)
     U2 = np.zeros((F, C, C), np.complex64)
@@ -295,6 +300,23 @@ def test_jackknife_coherence_kernel(C, F, T, K, output):
         rd2 += np.abs(d) ** 2
     np.testing.assert_allclose(sum_d, rd, rtol=1e-3, atol=2e-6 * T)
     np.testing.assert_allclose(sum_d2, rd2, rtol=2e-3, atol=1e-9)
+
+
+@pytest.mark.parametrize("case", JO.JACK_CASES, ids=JO.case_id)
+def test_jackknife_coherence_kernel_dispatch_edges(case):
+    """K9's kernel source at its dispatch edges against the float64 model and rounding bound of jack_oracle.py: both
+    staging paths (16 | 17 tapers), frequency counts around the 8-XCD mapping, one to five tile rows, launches of one
+    trial, every output kind; the sums continue across launches, the mirrored store is exact."""
+    C, F, T, K, kind, split = case
+    spec, S, direct, m = JO.case_data(case)
+    sum_d = np.zeros((F, C, C), np.complex128 if kind == "complex" else np.float64)
+    sum_d2 = np.zeros((F, C, C), np.float64)
+    t0 = 0
+    for n in split:
+        E.jack_coh_accumulate(spec[t0:t0 + n].reshape(-1, F, C), K, S, direct, kind, T, sum_d, sum_d2)
+        t0 += n
+    assert t0 == T
+    JO.check(sum_d, sum_d2, m, kind, "K9 emulated " + JO.case_id(case))
 
 
 @pytest.mark.parametrize("C,N,norm", [(5, 600, 0), (6, 301, 1), (3, 1400, 2)])
