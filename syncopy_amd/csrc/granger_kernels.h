@@ -12,6 +12,7 @@
 #pragma once
 #include "cd_math.h"
 #include "f64_stockham.h"
+#include "granger_route.h"      // tile constants, zgemm_tiles / zgemm_groups
 
 namespace spywil {
 
@@ -26,7 +27,6 @@ __global__ void __launch_bounds__(256) widen_kernel(const float2* in, cd* out, i
 }
 
 // ---- batched C[b] = A[b] * op(B[b]) (+ I), n x n, opB: 0 = B, 1 = B^H; strideB = 0 broadcasts B
-constexpr int GT = 32;   // output tile
 constexpr int GK = 8;    // k step
 __global__ void __launch_bounds__(256) zgemm_kernel(const cd* A, const cd* B, cd* Cm, int n, long long sA, long long sB,
                                                     long long sC, int opB, int addI) {
@@ -84,7 +84,6 @@ __global__ void __launch_bounds__(256) zgemm_kernel(const cd* A, const cd* B, cd
 //   Cr += Ar Br ; Cr += (-Ai) Bi ; Ci += Ar Bi ; Ci += Ai Br.
 // The 32 x 32 VALU tile above moves 16 bytes per 16 flop through L2 and stalls at ~28 TFLOP/s; this tile
 // halves the traffic per flop and leaves the multiply-adds to the matrix pipe.
-constexpr int MT = 64;   // output tile
 constexpr int MK = 8;    // k per stage
 // Badd (n x n, or nullptr): op(B) + Badd is multiplied - the skew matrix S of wilson_sf.py:97-98 joins g+ here instead
 // of in a pass of its own.  Ref / part (or nullptr): instead of storing C, the workgroup writes
@@ -96,11 +95,6 @@ constexpr int MK = 8;    // k per stage
 // MODE 0: plain, 1: with Badd, 2: error check (separate instances: the plain product keeps its 90 registers and
 // three waves per SIMD - with the extra operands in one kernel it dropped to two and ran at half speed)
 #define SPY_ZGEMM_KATTR SPY_WAVES_PER_EU(3, 3)
-// 64 x 64 output tiles per matrix: all of them, or the lower triangle for the Hermitian modes (2: error check, 3: X X^H)
-__host__ __device__ inline int zgemm_tiles(int n, bool hermitian) {
-    const int ntx = (n + 63) / 64;
-    return hermitian ? ntx * (ntx + 1) / 2 : ntx * ntx;
-}
 
 // one 64 x 64 output tile (by, bx) of matrix b; `pidx`: where MODE 2 leaves its maximum
 template <int MODE>
@@ -241,14 +235,7 @@ __device__ __forceinline__ void zgemm_tile(const cd* A, const cd* B, cd* Cm, int
 // The dispatcher hands out about one workgroup per microsecond and XCD, and a 64 x 64 x 256 tile is 28 us of matrix
 // work on a CU that holds three of them: with one tile per workgroup the DISPATCHER set the pace (the Hermitian modes
 // took as long as the full product while 6 of their 16 workgroups exited at once).  So the Hermitian modes launch
-// the lower-triangle tiles only (zgemm_tiles), and every workgroup works through zgemm_tpw(MODE) tiles.
-// (measured per mode at 2049 x 256 x 256: the plain product - whose four tiles of a row share the A panel - likes 4
-// tiles per workgroup, 3.66 -> 2.84 ms with the triangular factor; the others are best with 2)
-__host__ __device__ constexpr int zgemm_tpw(int mode) { return mode == 0 ? 4 : 2; }
-__host__ __device__ inline int zgemm_groups(int n, int mode) {
-    const int tpw = zgemm_tpw(mode);
-    return (zgemm_tiles(n, mode == 2 || mode == 3) + tpw - 1) / tpw;
-}
+// the lower-triangle tiles only (zgemm_tiles), and every workgroup works through zgemm_tpw(MODE) tiles (granger_route.h).
 
 template <int MODE>
 __global__ void __launch_bounds__(256) SPY_ZGEMM_KATTR zgemm_mfma_kernel(const cd* A, const cd* B, cd* Cm, int n, long long sA, long long sB,
@@ -317,7 +304,6 @@ __global__ void __launch_bounds__(256) maxred_kernel(const double* part, int n, 
 // The row block R (ZB x n) and D live in LDS.  Pivots are taken inside the diagonal block only, in
 // order: `info[b] = 2` flags a (relatively) tiny pivot - the caller then repeats with the pivoted
 // kernel.  Hermitian positive definite inputs (the CSD itself) never trip it.
-constexpr int ZB = 16;
 __global__ void __launch_bounds__(256) zinv_blocked_kernel(cd* M, int n, int* info) {
     SPY_DYN_SMEM(char, raw);
     const int npad = ((n + ZB - 1) / ZB) * ZB;
@@ -417,8 +403,6 @@ __global__ void __launch_bounds__(256) zinv_blocked_kernel(cd* M, int n, int* in
 // Twice the block size halves the sweeps over the matrix (8 x 2 MB instead of 16 x 2 MB at n = 256: the VALU
 // kernel sat at HBM / Infinity-Cache speed, 23 ms for 2049 matrices).  Pivots inside the diagonal block only, in
 // order; info = 2 flags a (relatively) tiny pivot exactly as zinv_blocked_kernel does.
-constexpr int ZM = 32;
-constexpr int ZT = 512;      // threads: 8 waves = two per SIMD (an MFMA blocks its wave; the partner keeps the pipe busy)
 constexpr int ZJ = 4;        // column tiles per pass of the trailing update: 8 independent accumulators per wave
 // `src` != nullptr: out of place - the first sweep reads src, everything lands in M (saves the caller a copy)
 __global__ void __launch_bounds__(ZT) zinv_mfma_kernel(cd* M, const cd* src, int n, int* info) {
@@ -602,7 +586,6 @@ __global__ void __launch_bounds__(ZT) zinv_mfma_kernel(cd* M, const cd* src, int
 // this version 7.5 (its parts ADD UP - memory skeleton 3.4 + diagonal blocks 1.6 + MFMA phases 3.0 - one workgroup per
 // CU runs them one after the other); two 4-wave workgroups per CU (R pieces parked in the rows of block k, D's LDS
 // reused for the panel) 9.2: 512 matrices in flight no longer fit the 256 MB Infinity Cache between sweeps.
-constexpr int ZW = 64;
 __global__ void __launch_bounds__(ZT) zinv64_mfma_kernel(cd* M, const cd* src, int n, int* info) {
     SPY_DYN_SMEM(char, raw);
     constexpr int LDD = ZW + 1;
@@ -923,7 +906,6 @@ __global__ void __launch_bounds__(256) zchol_kernel(cd* M, int n, int* info) {
 // panel is read once, receives the contributions of all earlier columns from registers (one thread per row, 32
 // accumulators; the 32 rows of L the panel's columns need are staged through LDS in chunks of 32 columns), is
 // factorised inside LDS and written once: ~3 MB per matrix.  Same arithmetic per element, other summation order.
-constexpr int CHP = 32;
 __global__ void __launch_bounds__(256) zchol_panel_kernel(cd* M, int n, int* info) {
     SPY_DYN_SMEM(char, raw);
     cd* P = reinterpret_cast<cd*>(raw);                  // n x (CHP + 1): the panel, row i at P[i * (CHP + 1)]

@@ -20,6 +20,7 @@
 // only known when this kernel has finished.
 #pragma once
 #include "cd_math.h"
+#include "granger_route.h"      // plus4_grid
 
 #define SPY_PLUS_KATTR SPY_MIN_WAVES_PER_EU(2)      // two workgroups of 4 waves per CU
 
@@ -226,7 +227,6 @@ __device__ __forceinline__ void p_pair(cd (&ga)[8], cd (&gb)[8], cd& gn_a, cd& g
 // g0: (nent).  Four consecutive pairs share the 128-byte lines of every row, so they are dealt to four workgroups that
 // the dispatcher places on the SAME XCD one after the other (block b -> XCD b % 8): the line is fetched from HBM once
 // and found in that XCD's L2 by the other three.  64 data registers, two workgroups per CU.
-__host__ __device__ inline long long plus4_grid(long long nent) { return (((nent + 1) / 2 + 31) / 32) * 32; }
 template <int LOG2L>
 __global__ void __launch_bounds__((PCfg<LOG2L>::T)) SPY_PLUS_KATTR plus4_kernel(const cd* g, int F, long long nent, const cd* tw, cd* gp, cd* g0) {
     using C = PCfg<LOG2L>;

@@ -546,34 +546,36 @@ def cwt_direct_fits(tpos, nsig, V, rowb, chanb):
     return bool(f(_p(tp, C.c_int), nsig, _p(v, C.c_int), v.size, rowb, chanb))
 
 
-# ---------------------------------------------------------------- Wilson / Granger (mirror of the host loop in granger.hip)
+# ---------------------------------------------------------------- Wilson / Granger (the sequence of spyhip_granger, granger.hip)
+# Every kernel choice below is the one of syncopy_amd/csrc/granger_route.h, taken by the emulator entry itself.
+LDS_PER_BLOCK = 160 * 1024          # sharedMemPerBlockOptin of the MI355X
+NUM_CU = 256
+
+
 def _dp(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def w_gemm(A, B, opB=0, addI=0):
+def _named(kernel, name):
+    if kernel is not None:
+        assert name.value.decode() == kernel, (name.value.decode(), kernel)
+
+
+def w_gemm(A, B, opB=0, addI=0, badd=None, ref=None, kernel=None):
+    """A op(B) (+ I) through the product kernel of the route.  n >= 48 only: `badd` (n, n) joins op(B); with `ref` the
+    return value is max |ref - A op(B)| / |ref| and no product is stored.  `kernel`: the kernel name the route must give."""
     A = np.ascontiguousarray(A, dtype=np.complex128)
     B = np.ascontiguousarray(B, dtype=np.complex128)
     batch, n = (A.shape[0], A.shape[1]) if A.ndim == 3 else (1, A.shape[0])
     sB = 0 if B.ndim == 2 and A.ndim == 3 else n * n
     out = np.zeros_like(A)
-    lib().emu_w_gemm(_dp(A), _dp(B), _dp(out), C.c_int(n), C.c_int(batch), C.c_longlong(n * n), C.c_longlong(sB),
-                     C.c_longlong(n * n), C.c_int(opB), C.c_int(addI))
-    return out
-
-
-def w_gemm_fused(A, B, opB=0, badd=None, ref=None):
-    """zgemm_mfma_kernel's fused forms (n >= 48): A op(B + ...) with `badd` (n, n) joined to op(B); with `ref` the
-    return value is max |ref - A op(B)| / |ref| and no product is stored."""
-    A = np.ascontiguousarray(A, dtype=np.complex128)
-    B = np.ascontiguousarray(B, dtype=np.complex128)
-    batch, n = A.shape[0], A.shape[1]
-    out = np.zeros_like(A)
     ba = None if badd is None else np.ascontiguousarray(badd, dtype=np.complex128)
     rf = None if ref is None else np.ascontiguousarray(ref, dtype=np.complex128)
-    lib().emu_w_gemm_fused.restype = C.c_double
-    err = lib().emu_w_gemm_fused(_dp(A), _dp(B), _dp(out), C.c_int(n), C.c_int(batch), C.c_longlong(n * n), C.c_int(opB),
-                                 _dp(ba), _dp(rf))
+    name = C.create_string_buffer(64)
+    lib().emu_w_gemm.restype = C.c_double
+    err = lib().emu_w_gemm(_dp(A), _dp(B), _dp(out), C.c_int(n), C.c_int(batch), C.c_longlong(n * n), C.c_longlong(sB),
+                           C.c_longlong(n * n), C.c_int(opB), C.c_int(addI), _dp(ba), _dp(rf), name)
+    _named(kernel, name)
     return err if ref is not None else out
 
 
@@ -585,38 +587,41 @@ def w_skew(g0):
     return S, g0S
 
 
-def w_inv(M, blocked=False):
+def w_inv(M, blocked=False, lds_per_block=LDS_PER_BLOCK, kernel=None):
+    """The inverse kernel the route gives for (n, blocked, lds_per_block); `kernel`: the name it must have."""
     M = np.array(M, dtype=np.complex128, order="C")
     batch, n = (M.shape[0], M.shape[1]) if M.ndim == 3 else (1, M.shape[0])
     info = np.zeros(batch, dtype=np.int32)
-    fn = {False: lib().emu_w_inv, True: lib().emu_w_inv_blocked, "mfma": lib().emu_w_inv_mfma,
-          "mfma64": lib().emu_w_inv_mfma64}[blocked]
-    fn(_dp(M), C.c_int(n), C.c_int(batch), _dp(info))
+    name = C.create_string_buffer(64)
+    lib().emu_w_inv(_dp(M), C.c_int(n), C.c_int(batch), _dp(info), C.c_int(bool(blocked)), C.c_ulonglong(lds_per_block), name)
+    _named(kernel, name)
     return M, info
 
 
-def w_plus(g, fast=False):
-    """Emulated plus operator on a half spectrum g (F, n, n) complex128 -> (gp (F, n, n), g0 (n, n)).
-    `fast`: plus4_kernel (power-of-two lag-domain lengths; two entries per complex transform)."""
+def w_plus(g, generic=False, kernel=None):
+    """Emulated plus operator on a half spectrum g (F, n, n) complex128 -> (gp (F, n, n), g0 (n, n)) on the kernel family
+    of the route; `generic`: plus_kernel (the radix-4 passes in LDS) whatever the length."""
     g = np.ascontiguousarray(g, dtype=np.complex128)
     F, n, _ = g.shape
     L = 2 * (F - 1)
     tw = np.ascontiguousarray(np.exp(-2j * np.pi * np.arange(L) / L))
     gp = np.zeros_like(g)
     g0 = np.zeros((n, n), dtype=np.complex128)
-    if fast:
-        rc = lib().emu_w_plus4(_dp(g), C.c_int(F), C.c_int(n), _dp(tw), _dp(gp), _dp(g0))
-        assert rc == 0, f"no plus4 kernel for F = {F}"
-        return gp, g0
-    lib().emu_w_plus(_dp(g), C.c_int(F), C.c_int(n), _dp(tw), _dp(gp), _dp(g0))     # returns the number of passes
+    name = C.create_string_buffer(64)
+    rc = lib().emu_w_plus(_dp(g), C.c_int(F), C.c_int(n), _dp(tw), _dp(gp), _dp(g0), C.c_ulonglong(LDS_PER_BLOCK),
+                          C.c_int(NUM_CU), C.c_int(bool(generic)), name)
+    assert rc == 0, f"no radix schedule for F = {F}"
+    _named(kernel, name)
     return gp, g0
 
 
-def w_chol(M):
+def w_chol(M, kernel=None):
     M = np.array(M, dtype=np.complex128, order="C")
     batch, n = (M.shape[0], M.shape[1]) if M.ndim == 3 else (1, M.shape[0])
     info = np.zeros(batch, dtype=np.int32)
-    lib().emu_w_chol(_dp(M), C.c_int(n), C.c_int(batch), _dp(info))
+    name = C.create_string_buffer(64)
+    lib().emu_w_chol(_dp(M), C.c_int(n), C.c_int(batch), _dp(info), C.c_ulonglong(LDS_PER_BLOCK), name)
+    _named(kernel, name)
     return M, info
 
 
@@ -631,11 +636,17 @@ def w_cond(A, iters=400):
     return float(np.nanmax(np.where(np.isnan(c), np.inf, c)))
 
 
+def w_err_route(n, F, forced=False):
+    """(fused, subset first, subset bins) of the convergence check (granger_route.h: err_route)."""
+    out = (C.c_int * 3)()
+    lib().emu_w_err_route(C.c_int(n), C.c_int(F), C.c_int(bool(forced)), out)
+    return bool(out[0]), bool(out[1]), out[2]
+
+
 def granger(csd64, rtol=5e-6, niter=100, cond_max=1e4, eps_max=1e-1, cond_iters=400):
     """Emulated spyhip_granger: csd64 (F, n, n) complex64 -> (granger float32, H, Sigma, info[4])."""
     csd64 = np.ascontiguousarray(csd64, dtype=np.complex64)
     F, n, _ = csd64.shape
-    L = 2 * (F - 1)
 
     def widen(eps):
         out = np.zeros((F, n, n), dtype=np.complex128)
@@ -657,30 +668,54 @@ def granger(csd64, rtol=5e-6, niter=100, cond_max=1e4, eps_max=1e-1, cond_iters=
     g0m = np.zeros((n, n), dtype=np.complex128)
     lib().emu_w_gamma0(_dp(A), C.c_int(F), C.c_int(n), _dp(g0m))
     Lc, info = w_chol(g0m)
-    psi0 = np.ascontiguousarray(Lc.T)
-    psi = np.ascontiguousarray(np.tile(psi0, (F, 1, 1)))
-    m = np.arange(L)
-    tw = np.ascontiguousarray(np.exp(-2j * np.pi * m / L))
-    converged, err = False, np.inf
-    for _ in range(niter):
-        pinv, _i = w_inv(psi)
-        T2 = w_gemm(pinv, U)
-        g = w_gemm(T2, T2, opB=1, addI=1)
-        gp = np.zeros_like(g)
-        g0 = np.zeros((n, n), dtype=np.complex128)
-        lib().emu_w_plus(_dp(g), C.c_int(F), C.c_int(n), _dp(tw), _dp(gp), _dp(g0))
-        g0S = np.zeros((n, n), dtype=np.complex128)
-        lib().emu_w_addS(_dp(gp), _dp(g0), _dp(g0S), C.c_int(F), C.c_int(n))
-        psi = w_gemm(psi, gp)
-        psi0 = w_gemm(psi0, g0S)
-        rec = w_gemm(psi, psi, opB=1)
-        lib().emu_w_relerr.restype = C.c_double
-        err = lib().emu_w_relerr(_dp(A), _dp(rec), C.c_longlong(F * n * n))
-        if err < rtol:
-            converged = True
+    psi0_first = np.ascontiguousarray(Lc.T)
+    fused, subset_first, Fs = w_err_route(n, F)
+    converged, err, subset_only = False, np.inf, False
+
+    def check(bins):          # the fused check over the bins `bins` of psi
+        return w_gemm(psi[bins], psi[bins], opB=1, ref=A[bins])
+    for blocked in (True, False):       # the block inverse first; a tiny pivot anywhere restarts with the pivoted kernel
+        psi0 = psi0_first.copy()
+        psi = np.ascontiguousarray(np.tile(psi0, (F, 1, 1)))
+        tiny = False
+        for _ in range(niter):
+            pinv, flags = w_inv(psi, blocked=blocked)
+            T2 = w_gemm(pinv, U, addI=2 if n >= 48 else 0)
+            g = w_gemm(T2, T2, opB=1, addI=1)
+            gp, g0 = w_plus(g)
+            if fused:
+                S, g0S = w_skew(g0)
+                psi = w_gemm(psi, gp, badd=S)
+            else:
+                g0S = np.zeros((n, n), dtype=np.complex128)
+                lib().emu_w_addS(_dp(gp), _dp(g0), _dp(g0S), C.c_int(F), C.c_int(n))
+                psi = w_gemm(psi, gp)
+            psi0 = w_gemm(psi0, g0S)
+            subset_only = False
+            if subset_first:
+                err = check(slice(0, None, 8))
+                subset_only = bool(err >= rtol or err != err)
+            if fused:
+                if not subset_only:
+                    err = check(slice(None))
+            else:
+                rec = w_gemm(psi, psi, opB=1)
+                lib().emu_w_relerr.restype = C.c_double
+                err = lib().emu_w_relerr(_dp(A), _dp(rec), C.c_longlong(F * n * n))
+            tiny = bool((flags == 2).any())
+            if tiny:
+                break
+            if err < rtol:
+                converged = True
+                break
+        if not tiny:
             break
+    if not converged and subset_only:
+        err = check(slice(None))
     Sigma = w_gemm(psi0, psi0, opB=1)
-    p0i, _i = w_inv(psi0)
+    p0i, flags = w_inv(psi0, blocked=True)
+    if flags[0]:
+        p0i, _i = w_inv(psi0)
     H = w_gemm(psi, p0i)
     G = np.zeros((F, n, n), dtype=np.float32)
     lib().emu_w_granger(_dp(A), _dp(H), _dp(np.ascontiguousarray(Sigma)), C.c_int(F), C.c_int(n), _dp(G))

@@ -132,12 +132,11 @@ static void emu_launch_ccov(const spyfft::CcovArgs& a) {
     emu::launch(dim3((unsigned)grid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::ccov_lags_kernel<LOG2N, G>(a); });
 }
 
-// plus4_kernel (power-of-two lag-domain lengths 256 .. 4096); returns 0, or 1 if there is no such kernel for F
+// plus4_kernel<LOG2L> with the grid, threads and LDS of its route (granger_route.h)
 template <int LOG2L>
-void run_plus4(const double* g, int F, int n, const double* tw, double* gp, double* g0) {
-    using C = spywil::PCfg<LOG2L>;
-    emu::launch(dim3((unsigned)spywil::plus4_grid((long long)n * n)), dim3(C::T), C::LDS_BYTES, [&] {
-        spywil::plus4_kernel<LOG2L>(reinterpret_cast<const spywil::cd*>(g), F, (long long)n * n, reinterpret_cast<const spywil::cd*>(tw),
+void run_plus4(const spywil::PlusRoute& r, const double* g, int F, long long nent, const double* tw, double* gp, double* g0) {
+    emu::launch(dim3((unsigned)r.grid), dim3(r.threads), r.lds, [&] {
+        spywil::plus4_kernel<LOG2L>(reinterpret_cast<const spywil::cd*>(g), F, nent, reinterpret_cast<const spywil::cd*>(tw),
                                     reinterpret_cast<spywil::cd*>(gp), reinterpret_cast<spywil::cd*>(g0)); });
 }
 
@@ -842,99 +841,106 @@ int emu_cwt_direct_fits(const int* tpos, int nsig, const int* V, int ngroups, un
     return spycwt::cwt_direct_fits(tpos, nsig, V, ngroups, rowb, chanb) ? 1 : 0;
 }
 
-// ---- Wilson / Granger kernels, one entry per kernel (the Python test re-creates the host loop of granger.hip)
+// ---- Wilson / Granger kernels.  Which kernel an entry runs, with which grid and LDS, is the decision of granger_route.h
+// that granger.hip launches by; `name` (64 bytes, or NULL) receives the kernel's name.
 using spywil::cd;
+static void w_name(char* name, const char* s) { if (name) std::snprintf(name, 64, "%s", s); }
 void emu_w_widen(const float* in, double* out, int C, long long n, double eps) {
     emu::launch(dim3(4), dim3(256), 0, [&] { spywil::widen_kernel(reinterpret_cast<const float2*>(in), reinterpret_cast<cd*>(out), C, n, eps); });
 }
-void emu_w_gemm(const double* A, const double* B, double* Cm, int n, int batch, long long sA, long long sB, long long sC, int opB, int addI) {
-    if (n >= 48) {      // as granger.hip: fp64 MFMA tiles
-        const bool herm = opB == 1 && A == B && sA == sB;
-        dim3 g(spywil::zgemm_groups(n, herm ? 3 : 0) * ((batch + 7) / 8) * 8);
-        if (herm)     // as granger.hip: X X^H takes the Hermitian instance (lower-triangle tiles only)
-            emu::launch(g, dim3(256), 0, [&] { spywil::zgemm_mfma_kernel<3>(reinterpret_cast<const cd*>(A), reinterpret_cast<const cd*>(B), reinterpret_cast<cd*>(Cm), n, sA, sB, sC, opB, addI, nullptr, nullptr, nullptr, batch); });
-        else
-            emu::launch(g, dim3(256), 0, [&] { spywil::zgemm_mfma_kernel<0>(reinterpret_cast<const cd*>(A), reinterpret_cast<const cd*>(B), reinterpret_cast<cd*>(Cm), n, sA, sB, sC, opB, addI, nullptr, nullptr, nullptr, batch); });
-        return;
+// Badd (n x n) joins op(B); with Ref the return value is max |Ref - A op(B)| / |Ref| and no product is stored (both: n >= 48)
+double emu_w_gemm(const double* A_, const double* B_, double* C_, int n, int batch, long long sA, long long sB, long long sC, int opB,
+                  int addI, const double* Badd_, const double* Ref_, char* name) {
+    const cd *A = reinterpret_cast<const cd*>(A_), *B = reinterpret_cast<const cd*>(B_), *Badd = reinterpret_cast<const cd*>(Badd_),
+             *Ref = reinterpret_cast<const cd*>(Ref_);
+    cd* Cm = reinterpret_cast<cd*>(C_);
+    const spywil::GemmRoute r = spywil::gemm_route(n, batch, opB, A == B && sA == sB, Badd != nullptr, Ref != nullptr);
+    w_name(name, r.name);
+    std::vector<double> partv((size_t)r.ntiles * batch + 1, -1.0);
+    double* part = Ref ? partv.data() : nullptr;
+    const dim3 grid(r.grid.x, r.grid.y, r.grid.z);
+    switch (r.kernel) {
+        case spywil::Gemm::TILED: emu::launch(grid, dim3(r.threads), r.lds, [&] { spywil::zgemm_kernel(A, B, Cm, n, sA, sB, sC, opB, addI); }); break;
+        case spywil::Gemm::MFMA0: emu::launch(grid, dim3(r.threads), r.lds, [&] { spywil::zgemm_mfma_kernel<0>(A, B, Cm, n, sA, sB, sC, opB, addI, Badd, Ref, part, batch); }); break;
+        case spywil::Gemm::MFMA1: emu::launch(grid, dim3(r.threads), r.lds, [&] { spywil::zgemm_mfma_kernel<1>(A, B, Cm, n, sA, sB, sC, opB, addI, Badd, Ref, part, batch); }); break;
+        case spywil::Gemm::MFMA2: emu::launch(grid, dim3(r.threads), r.lds, [&] { spywil::zgemm_mfma_kernel<2>(A, B, Cm, n, sA, sB, sC, opB, addI, Badd, Ref, part, batch); }); break;
+        case spywil::Gemm::MFMA3: emu::launch(grid, dim3(r.threads), r.lds, [&] { spywil::zgemm_mfma_kernel<3>(A, B, Cm, n, sA, sB, sC, opB, addI, Badd, Ref, part, batch); }); break;
     }
-    dim3 grid((n + 31) / 32, (n + 31) / 32, batch);
-    emu::launch(grid, dim3(256), 0, [&] { spywil::zgemm_kernel(reinterpret_cast<const cd*>(A), reinterpret_cast<const cd*>(B), reinterpret_cast<cd*>(Cm), n, sA, sB, sC, opB, addI); });
-}
-// the fused forms of the matrix-core gemm: op(B) + Badd, and max |Ref - A op(B)| / |Ref| instead of the product
-double emu_w_gemm_fused(const double* A, const double* B, double* Cm, int n, int batch, long long sB, int opB, const double* Badd,
-                        const double* Ref) {
-    const int ntile = spywil::zgemm_tiles(n, Ref != nullptr);
-    dim3 g(spywil::zgemm_groups(n, Ref ? 2 : 1) * ((batch + 7) / 8) * 8);
-    std::vector<double> part((size_t)ntile * batch, -1.0);
-    emu::launch(g, dim3(256), 0, [&] {
-        if (Ref)
-            spywil::zgemm_mfma_kernel<2>(reinterpret_cast<const cd*>(A), reinterpret_cast<const cd*>(B), reinterpret_cast<cd*>(Cm), n,
-                                         (long long)n * n, sB, (long long)n * n, opB, 0, nullptr, reinterpret_cast<const cd*>(Ref), part.data(), batch);
-        else
-            spywil::zgemm_mfma_kernel<1>(reinterpret_cast<const cd*>(A), reinterpret_cast<const cd*>(B), reinterpret_cast<cd*>(Cm), n,
-                                         (long long)n * n, sB, (long long)n * n, opB, 0, reinterpret_cast<const cd*>(Badd), nullptr, nullptr, batch); });
-    if (!Ref) return 0.0;
+    if (r.kernel != spywil::Gemm::MFMA2) return 0.0;
     double out = -1.0;
-    emu::launch(dim3(1), dim3(256), 0, [&] { spywil::maxred_kernel(part.data(), (int)part.size(), &out); });
+    emu::launch(dim3(1), dim3(256), 0, [&] { spywil::maxred_kernel(part, r.ntiles * batch, &out); });
     return out;
 }
 void emu_w_skew(const double* g0, double* S, double* g0S, int n) {
     emu::launch(dim3((n * n + 255) / 256), dim3(256), 0, [&] { spywil::skew_kernel(reinterpret_cast<const cd*>(g0), reinterpret_cast<cd*>(S), reinterpret_cast<cd*>(g0S), n); });
 }
-void emu_w_inv(double* M, int n, int batch, int* info) {
-    emu::launch(dim3(batch), dim3(256), (size_t)n * 36, [&] { spywil::zinv_kernel(reinterpret_cast<cd*>(M), n, info); });
-}
-void emu_w_inv_blocked(double* M, int n, int batch, int* info) {
-    const int npad = ((n + spywil::ZB - 1) / spywil::ZB) * spywil::ZB;
-    emu::launch(dim3(batch), dim3(256), ((size_t)spywil::ZB * npad + spywil::ZB * spywil::ZB) * 16,
-                [&] { spywil::zinv_blocked_kernel(reinterpret_cast<cd*>(M), n, info); });
-}
-void emu_w_inv_mfma(double* M, int n, int batch, int* info) {
-    const int npad = ((n + spywil::ZM - 1) / spywil::ZM) * spywil::ZM;
-    // out of place from a copy of the input, as the Wilson iteration calls it
-    std::vector<double> src(M, M + (size_t)batch * n * n * 2);
-    std::fill(M, M + (size_t)batch * n * n * 2, -777.0);
-    emu::launch(dim3(batch), dim3(spywil::ZT), ((size_t)spywil::ZM * (npad + 1) + spywil::ZM * (spywil::ZM + 1)) * 16,
-                [&] { spywil::zinv_mfma_kernel(reinterpret_cast<cd*>(M), reinterpret_cast<const cd*>(src.data()), n, info); });
-}
-void emu_w_inv_mfma64(double* M, int n, int batch, int* info) {
-    std::vector<double> src(M, M + (size_t)batch * n * n * 2);
-    std::fill(M, M + (size_t)batch * n * n * 2, -777.0);
-    emu::launch(dim3(batch), dim3(spywil::ZT), (size_t)2 * spywil::ZW * (spywil::ZW + 1) * 16,
-                [&] { spywil::zinv64_mfma_kernel(reinterpret_cast<cd*>(M), reinterpret_cast<const cd*>(src.data()), n, info); });
-}
-void emu_w_chol(double* M, int n, int batch, int* info) {
-    if (n <= 256 && n >= 2 * spywil::CHP) {       // as granger.hip: the panel kernel
-        const size_t plds = ((size_t)n * (spywil::CHP + 1) + spywil::CHP * (spywil::CHP + 1)) * 16;
-        emu::launch(dim3(batch), dim3(256), plds, [&] { spywil::zchol_panel_kernel(reinterpret_cast<cd*>(M), n, info); });
-        return;
+// inverse of `batch` matrices in M, out of place from a copy of the input as the Wilson iteration calls it (M is
+// overwritten first, so a kernel that read M instead of its source would show)
+void emu_w_inv(double* M_, int n, int batch, int* info, int blocked, unsigned long long lds_per_block, char* name) {
+    const spywil::InvRoute r = spywil::inv_route(n, blocked != 0, true, (size_t)lds_per_block);
+    w_name(name, r.name);
+    const size_t cnt = (size_t)batch * n * n;
+    cd* M = reinterpret_cast<cd*>(M_);
+    std::vector<cd> srcv(M, M + cnt);
+    const cd* src = srcv.data();
+    std::fill(M_, M_ + 2 * cnt, -777.0);
+    if (r.copy_src) std::copy(src, src + cnt, M);
+    switch (r.kernel) {
+        case spywil::Inv::MFMA64: emu::launch(dim3(batch), dim3(r.threads), r.lds, [&] { spywil::zinv64_mfma_kernel(M, src, n, info); }); break;
+        case spywil::Inv::MFMA32: emu::launch(dim3(batch), dim3(r.threads), r.lds, [&] { spywil::zinv_mfma_kernel(M, src, n, info); }); break;
+        case spywil::Inv::BLOCKED16: emu::launch(dim3(batch), dim3(r.threads), r.lds, [&] { spywil::zinv_blocked_kernel(M, n, info); }); break;
+        case spywil::Inv::PIVOTED: emu::launch(dim3(batch), dim3(r.threads), r.lds, [&] { spywil::zinv_kernel(M, n, info); }); break;
     }
-    emu::launch(dim3(batch), dim3(256), (size_t)n * 16, [&] { spywil::zchol_kernel(reinterpret_cast<cd*>(M), n, info); });
+}
+void emu_w_chol(double* M, int n, int batch, int* info, unsigned long long lds_per_block, char* name) {
+    const spywil::CholRoute r = spywil::chol_route(n, (size_t)lds_per_block);
+    w_name(name, r.name);
+    if (r.kernel == spywil::Chol::PANEL) emu::launch(dim3(batch), dim3(r.threads), r.lds, [&] { spywil::zchol_panel_kernel(reinterpret_cast<cd*>(M), n, info); });
+    else emu::launch(dim3(batch), dim3(r.threads), r.lds, [&] { spywil::zchol_kernel(reinterpret_cast<cd*>(M), n, info); });
 }
 void emu_w_gamma0(const double* A, int F, int n, double* out) {
     emu::launch(dim3((n * n + 255) / 256), dim3(256), 0, [&] { spywil::gamma0_kernel(reinterpret_cast<const cd*>(A), F, n, reinterpret_cast<cd*>(out), 0, F); });
 }
-int emu_w_plus(const double* g, int F, int n, const double* tw, double* gp, double* g0) {
-    spywil::PlusPlan pl{};
+// the plus operator on the kernel family of the route; generic != 0: plus_kernel whatever the length (the radix-4 kernel
+// plus4_kernel is compared with).  Returns -3 where no radix schedule exists.
+int emu_w_plus(const double* g_, int F, int n, const double* tw_, double* gp_, double* g0_, unsigned long long lds_per_block, int num_cu,
+               int generic, char* name) {
+    const cd *g = reinterpret_cast<const cd*>(g_), *tw = reinterpret_cast<const cd*>(tw_);
+    cd *gp = reinterpret_cast<cd*>(gp_), *g0 = reinterpret_cast<cd*>(g0_);
     const int L = 2 * (F - 1);
-    pl.L = L;
-    int k = 0, m = L;
-    const int cand[] = {4, 2, 3, 5, 7, 11, 13};
-    for (int c : cand) while (m % c == 0 && m > 1) { pl.radix[k++] = c; m /= c; }
-    for (int p = 17; m > 1; p += 2) while (m % p == 0) { pl.radix[k++] = p; m /= p; }
-    pl.nfac = k;
-    emu::launch(dim3(n * n), dim3(256), (size_t)2 * L * 16, [&] { spywil::plus_kernel(reinterpret_cast<const cd*>(g), F, (long long)n * n, pl, reinterpret_cast<const cd*>(tw), reinterpret_cast<cd*>(gp), reinterpret_cast<cd*>(g0)); });
-    return k;
-}
-int emu_w_plus4(const double* g, int F, int n, const double* tw, double* gp, double* g0) {
-    switch (2 * (F - 1)) {
-        case 256: run_plus4<8>(g, F, n, tw, gp, g0); return 0;
-        case 512: run_plus4<9>(g, F, n, tw, gp, g0); return 0;
-        case 1024: run_plus4<10>(g, F, n, tw, gp, g0); return 0;
-        case 2048: run_plus4<11>(g, F, n, tw, gp, g0); return 0;
-        case 4096: run_plus4<12>(g, F, n, tw, gp, g0); return 0;
-        default: return 1;
+    const long long nent = (long long)n * n;
+    spywil::PlusPlan pl{};
+    if (!spywil::plus_plan(L, &pl)) return -3;
+    spywil::PlusRoute r = spywil::plus_route(L, nent, (size_t)lds_per_block, num_cu);
+    if (generic) { r = spywil::PlusRoute(); r.name = "spywil::plus_kernel"; r.grid = nent; r.lds = (size_t)2 * L * 16; }
+    w_name(name, r.name);
+    switch (r.kernel) {
+        case spywil::Plus::PLUS4:
+            switch (r.log2l) {
+                case 8: run_plus4<8>(r, g_, F, nent, tw_, gp_, g0_); break;
+                case 9: run_plus4<9>(r, g_, F, nent, tw_, gp_, g0_); break;
+                case 10: run_plus4<10>(r, g_, F, nent, tw_, gp_, g0_); break;
+                case 11: run_plus4<11>(r, g_, F, nent, tw_, gp_, g0_); break;
+                default: run_plus4<12>(r, g_, F, nent, tw_, gp_, g0_); break;
+            }
+            break;
+        case spywil::Plus::LDS:
+            emu::launch(dim3((unsigned)r.grid), dim3(r.threads), r.lds, [&] { spywil::plus_kernel(g, F, nent, pl, tw, gp, g0); });
+            break;
+        case spywil::Plus::LONG: {
+            std::vector<cd> scr(r.scratch_bytes / sizeof(cd));
+            for (long long e0 = 0; e0 < nent; e0 += r.chunk)
+                emu::launch(dim3((unsigned)std::min(r.chunk, nent - e0)), dim3(r.threads), 0,
+                            [&] { spywil::plus_long_kernel(g, F, nent, pl, tw, gp, g0, scr.data(), e0); });
+            break;
+        }
     }
+    return 0;
+}
+// the convergence check of the Wilson iteration for n channels and F bins: out = {fused, subset first, subset bins}
+void emu_w_err_route(int n, int F, int full_check_forced, int* out) {
+    const spywil::ErrRoute r = spywil::err_route(n, F, full_check_forced != 0);
+    out[0] = r.fused; out[1] = r.subset_first; out[2] = r.subset_bins;
 }
 void emu_w_addS(double* gp, const double* g0, double* out0, int F, int n) {
     emu::launch(dim3(4), dim3(256), 0, [&] { spywil::add_S_kernel(reinterpret_cast<cd*>(gp), reinterpret_cast<const cd*>(g0), reinterpret_cast<cd*>(out0), F, n); });

@@ -668,50 +668,53 @@ def test_cwt_direct_kernels_gapped_slots(output):
 
 @pytest.mark.parametrize("n", [32, 37, 70])
 def test_blocked_inverse(n):
-    """Block Gauss-Jordan inverse (16 x 16 diagonal blocks): ragged sizes, identity padding, tiny-pivot flag."""
+    """Block Gauss-Jordan inverse (16 x 16 diagonal blocks): ragged sizes, identity padding, tiny-pivot flag.  The route
+    gives this kernel below 64 channels, and at 70 where 64 KiB of LDS do not hold the 32-row kernel's row block."""
     rng = np.random.default_rng(n)
     B = 2
     A = rng.normal(size=(B, n, n)) + 1j * rng.normal(size=(B, n, n)) + 3 * np.sqrt(n) * np.eye(n)
-    inv, info = E.w_inv(A, blocked=True)
+    kw = dict(blocked=True, lds_per_block=64 * 1024, kernel="spywil::zinv_blocked_kernel")
+    inv, info = E.w_inv(A, **kw)
     assert not info.any()
     np.testing.assert_allclose(inv @ A, np.tile(np.eye(n), (B, 1, 1)), atol=1e-10)
     P = np.zeros((1, n, n), complex)
     P[0] = np.eye(n)[::-1]                     # anti-diagonal permutation: every leading block is singular
-    _, info = E.w_inv(P, blocked=True)
+    _, info = E.w_inv(P, **kw)
     assert info[0] == 2
 
 
-@pytest.mark.parametrize("n", [64, 37, 70, 97])
+@pytest.mark.parametrize("n", [64, 65, 70, 97])
 def test_blocked_inverse_on_f64_matrix_cores(n):
     """zinv_mfma_kernel (32 x 32 blocks, R = D A_k* and the trailing update as v_mfma_f64_16x16x4_f64 tiles): ragged
-    sizes (identity padding, partial tiles), asymmetric complex matrices (a row/column swap of a fragment layout would
-    show), the tiny-pivot flag."""
+    sizes (identity padding, partial tiles; 65: one row in the last block), asymmetric complex matrices (a row/column
+    swap of a fragment layout would show), the tiny-pivot flag.  Sizes the route sends to this kernel (64 ... 127)."""
     rng = np.random.default_rng(n)
     B = 2
     A = rng.normal(size=(B, n, n)) + 1j * rng.normal(size=(B, n, n)) + 3 * np.sqrt(n) * np.eye(n)
-    inv, info = E.w_inv(A, blocked="mfma")
+    inv, info = E.w_inv(A, blocked=True, kernel="spywil::zinv_mfma_kernel")
     assert not info.any()
     np.testing.assert_allclose(inv, np.linalg.inv(A), rtol=1e-9, atol=1e-11)
     P = np.zeros((1, n, n), complex)
     P[0] = np.eye(n)[::-1]
-    _, info = E.w_inv(P, blocked="mfma")
+    _, info = E.w_inv(P, blocked=True, kernel="spywil::zinv_mfma_kernel")
     assert info[0] == 2
 
 
-@pytest.mark.parametrize("n", [128, 100, 192, 64, 161])
+@pytest.mark.parametrize("n", [128, 176, 192, 161])
 def test_blocked_inverse_with_64_row_blocks(n):
     """zinv64_mfma_kernel (64 x 64 diagonal blocks, the matrix walked in column quarters through a 64 x 64 R panel in
-    LDS, the quarter of the block itself last): ragged sizes, asymmetric complex matrices, out of place, the tiny-pivot
-    flag."""
+    LDS, the quarter of the block itself last): ragged sizes (161: one row in the last block, 176: a whole 16-row tile
+    of padding), asymmetric complex matrices, out of place, the tiny-pivot flag.  Sizes the route sends to this kernel
+    (from 128 on, where 64-row blocks pad no more than 32-row blocks)."""
     rng = np.random.default_rng(n)
     B = 1 if n > 128 else 2            # (one OS thread per GPU thread: 192 x 192 costs 20 s per matrix)
     A = rng.normal(size=(B, n, n)) + 1j * rng.normal(size=(B, n, n)) + 3 * np.sqrt(n) * np.eye(n)
-    inv, info = E.w_inv(A, blocked="mfma64")
+    inv, info = E.w_inv(A, blocked=True, kernel="spywil::zinv64_mfma_kernel")
     assert not info.any()
     np.testing.assert_allclose(inv, np.linalg.inv(A), rtol=1e-9, atol=1e-11)
     P = np.zeros((1, n, n), complex)
     P[0] = np.eye(n)[::-1]
-    _, info = E.w_inv(P, blocked="mfma64")
+    _, info = E.w_inv(P, blocked=True, kernel="spywil::zinv64_mfma_kernel")
     assert info[0] == 2
 
 
@@ -724,7 +727,7 @@ def test_plus_operator(F):
     full[:F] = g
     full[F:] = np.conj(g[1:F - 1][::-1])
     ref, ref0 = O.plus_operator(full)
-    gp, g0 = E.w_plus(g)
+    gp, g0 = E.w_plus(g, kernel="spywil::plus_kernel")
     np.testing.assert_allclose(gp, ref[:F], rtol=1e-12, atol=1e-12)
     np.testing.assert_allclose(g0, ref0, rtol=1e-12, atol=1e-12)
 
@@ -741,10 +744,10 @@ def test_plus_operator_two_entries_per_transform(F, n):
     full[:F] = g
     full[F:] = np.conj(g[1:F - 1][::-1])
     ref, ref0 = O.plus_operator(full)
-    gp, g0 = E.w_plus(g, fast=True)
+    gp, g0 = E.w_plus(g, kernel="spywil::plus4_kernel<%d>" % (L.bit_length() - 1))
     np.testing.assert_allclose(gp, ref[:F], rtol=1e-12, atol=1e-12)
     np.testing.assert_allclose(g0, ref0, rtol=1e-12, atol=1e-12)
-    old, old0 = E.w_plus(g)
+    old, old0 = E.w_plus(g, generic=True, kernel="spywil::plus_kernel")
     np.testing.assert_allclose(gp, old, rtol=1e-12, atol=1e-12)
 
 
@@ -755,7 +758,7 @@ def test_zgemm_on_f64_matrix_cores():
     n = 50
     A = rng.normal(size=(1, n, n)) + 1j * rng.normal(size=(1, n, n))
     Bm = rng.normal(size=(1, n, n)) + 1j * rng.normal(size=(1, n, n))
-    np.testing.assert_allclose(E.w_gemm(A, Bm), A @ Bm, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(E.w_gemm(A, Bm, kernel="spywil::zgemm_mfma_kernel<0>"), A @ Bm, rtol=1e-12, atol=1e-12)
     np.testing.assert_allclose(E.w_gemm(A, Bm, opB=1, addI=1), A @ Bm.conj().transpose(0, 2, 1) + np.eye(n), rtol=1e-12,
                                atol=1e-12)
     # addI & 2: B declared lower triangular (the Cholesky factor): the zero rows above a column tile are skipped
@@ -778,13 +781,13 @@ def test_zgemm_fused_skew_and_error_check():
     Sref = np.triu(g0) - np.triu(g0).conj().T
     np.testing.assert_allclose(S, Sref, rtol=0, atol=0)
     np.testing.assert_allclose(g0S, g0 + Sref, rtol=1e-15)
-    np.testing.assert_allclose(E.w_gemm_fused(psi, gp, badd=S), psi @ (gp + Sref), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(E.w_gemm(psi, gp, badd=S, kernel="spywil::zgemm_mfma_kernel<1>"), psi @ (gp + Sref), rtol=1e-12, atol=1e-12)
     # X X^H + I through the Hermitian instance (lower tiles computed, mirrored above the diagonal)
-    np.testing.assert_allclose(E.w_gemm(psi, psi, opB=1, addI=1), psi @ psi.conj().transpose(0, 2, 1) + np.eye(n),
-                               rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(E.w_gemm(psi, psi, opB=1, addI=1, kernel="spywil::zgemm_mfma_kernel<3>"),
+                               psi @ psi.conj().transpose(0, 2, 1) + np.eye(n), rtol=1e-12, atol=1e-12)
     herm = rng.normal(size=(B, n, n)) * 1e-3
     ref = psi @ psi.conj().transpose(0, 2, 1) * (1 + herm + herm.transpose(0, 2, 1))        # Hermitian reference
-    err = E.w_gemm_fused(psi, psi, opB=1, ref=ref)
+    err = E.w_gemm(psi, psi, opB=1, ref=ref, kernel="spywil::zgemm_mfma_kernel<2>")
     np.testing.assert_allclose(err, O.max_rel_err(ref, psi @ psi.conj().transpose(0, 2, 1)), rtol=1e-10)
 
 
@@ -794,8 +797,8 @@ def test_hermitian_zgemm_ragged_tiles(n):
     tile row whose mirror fills the column above it (65); nine matrices, so the batch is not a multiple of 8."""
     rng = np.random.default_rng(n)
     X = rng.normal(size=(9, n, n)) + 1j * rng.normal(size=(9, n, n))
-    np.testing.assert_allclose(E.w_gemm(X, X, opB=1, addI=1), X @ X.conj().transpose(0, 2, 1) + np.eye(n), rtol=1e-12,
-                               atol=1e-12)
+    np.testing.assert_allclose(E.w_gemm(X, X, opB=1, addI=1, kernel="spywil::zgemm_mfma_kernel<3>"),
+                               X @ X.conj().transpose(0, 2, 1) + np.eye(n), rtol=1e-12, atol=1e-12)
 
 
 def test_wilson_building_blocks():
@@ -806,12 +809,12 @@ def test_wilson_building_blocks():
     np.testing.assert_allclose(E.w_gemm(A, Bm), A @ Bm, rtol=1e-12, atol=1e-12)
     np.testing.assert_allclose(E.w_gemm(A, Bm, opB=1, addI=1), A @ Bm.conj().transpose(0, 2, 1) + np.eye(n), rtol=1e-12,
                                atol=1e-12)
-    np.testing.assert_allclose(E.w_gemm(A, Bm[0]), A @ Bm[0], rtol=1e-12, atol=1e-12)        # broadcast B
-    inv, info = E.w_inv(A)
+    np.testing.assert_allclose(E.w_gemm(A, Bm[0], kernel="spywil::zgemm_kernel"), A @ Bm[0], rtol=1e-12, atol=1e-12)        # broadcast B
+    inv, info = E.w_inv(A, kernel="spywil::zinv_kernel")
     assert not info.any()
     np.testing.assert_allclose(inv @ A, np.tile(np.eye(n), (B, 1, 1)), atol=1e-9)
     P = A @ A.conj().transpose(0, 2, 1) + n * np.eye(n)
-    Lc, info = E.w_chol(P)
+    Lc, info = E.w_chol(P, kernel="spywil::zchol_kernel")
     assert not info.any()
     np.testing.assert_allclose(Lc, np.linalg.cholesky(P), rtol=1e-10, atol=1e-10)
     assert abs(E.w_cond(P[:1, :9, :9].copy(), iters=40) / np.linalg.cond(P[0, :9, :9]) - 1) < 5e-2
@@ -825,7 +828,7 @@ def test_panel_cholesky(n):
     X = rng.normal(size=(3, n, n)) + 1j * rng.normal(size=(3, n, n))
     P = X @ X.conj().transpose(0, 2, 1) + 0.5 * n * np.eye(n)
     P[2, 40, 40] = -1.0                                        # third matrix: indefinite
-    Lc, info = E.w_chol(P)
+    Lc, info = E.w_chol(P, kernel="spywil::zchol_panel_kernel")
     assert list(info) == [0, 0, 1]
     np.testing.assert_allclose(Lc[:2], np.linalg.cholesky(P[:2]), rtol=1e-10, atol=1e-10)
     assert np.all(np.triu(Lc[:2], 1) == 0)

@@ -1,27 +1,11 @@
 """K6 (csrc/granger.hip, granger_kernels.h, wilson_plus_kernel.h) on the device at every size class of its kernel
 dispatch, against NumPy complex128 (oracle/spy_oracle.py or plain np.linalg).
 
-granger.hip picks its kernels by the channel count n in gemm(), invert() and cholesky().  With ZB = 16, ZM = 32,
-ZW = 64, CHP = 32, MT = 64 and the 160 KiB of LDS per workgroup that the MI355X reports (sharedMemPerBlockOptin):
+granger.hip picks its kernels by the channel count n and the LDS per workgroup (160 KiB on the MI355X), through
+csrc/granger_route.h; tests/test_granger_route.py holds the table of size classes and checks the route against it for
+every n up to 512.
 
-    n                       products                     inverse in the iteration           Cholesky
-    < 32                    zgemm_kernel                 zinv_kernel (pivoted)              zchol_kernel
-    32 ... 47               zgemm_kernel                 zinv_blocked_kernel (16-row)       zchol_kernel
-    48 ... 63               zgemm_mfma_kernel<0..3>      zinv_blocked_kernel                zchol_kernel
-                            (ragged 64 x 64 tiles)
-    64 ... 127, 129 ... 160,
-    193 ... 224             MFMA                         zinv_mfma_kernel (32-row blocks)   zchol_panel_kernel
-    128, 161 ... 192,
-    225 ... 256             MFMA                         zinv64_mfma_kernel (64-row)        zchol_panel_kernel
-    257 ... 288, 321 ... 352,
-    385 ... 416             MFMA                         zinv_blocked_kernel (the 32-row    zchol_kernel
-                                                         kernel no longer fits LDS)
-    289 ... 320, 353 ... 384 MFMA                        zinv64_mfma_kernel                 zchol_kernel
-
-(zinv64_mfma_kernel wherever n >= 128 and 64-row blocks pad no more than 32-row blocks would; otherwise
-zinv_mfma_kernel while its (32 (npad + 1) + 32 * 33) x 16 bytes fit LDS, zinv_blocked_kernel beyond.)
-
-N below touches every row from 48 up, and every ragged form of each: 48 / 63 (16-row blocks, ragged MFMA tiles),
+N below touches every row of that table from 48 up, and every ragged form of each: 48 / 63 (16-row blocks, ragged MFMA tiles),
 65 / 100 (32-row blocks, ragged last block, ragged last Cholesky panel), 128 (two full 64-row blocks), 161 / 255
 (ragged last 64-row block and Cholesky panel), 200 (32-row blocks, ragged last one), 257 (16-row blocks above 256,
 the column Cholesky), 300 (ragged 64-row blocks with the column Cholesky).  profiles/wilson_dispatch_kernels.txt is
