@@ -1,7 +1,10 @@
 // Small fp64 host FFT (iterative radix-2) used once per plan to build filter spectra
-// (Bluestein chirp filter, Morlet kernel spectra), the twiddle tables and the Bluestein tables the plans upload.
+// (Bluestein chirp filter, Morlet kernel spectra), and the host tables the plans upload: twiddles, Bluestein tables, taper
+// moments, the pre-scaled windows and the frequency map.  Pure functions, no HIP header (tests/test_fft_tables.py).
 #pragma once
 #include <cmath>
+#include <cstdio>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -74,5 +77,41 @@ void bluestein_tables(int nfft, int M, int M1, std::vector<T2>* chirp, std::vect
             (*bhat)[(size_t)k1 * M2 + k2].x = (T)(br[k] / M);
             (*bhat)[(size_t)k1 * M2 + k2].y = (T)(bi[k] / M);
         }
+}
+
+// [ntaper][2]: sum w_k, sum w_k (n - mid) of the float32 windows (trend removal of the transforms through HBM)
+inline std::vector<double> taper_moments(const std::vector<float>& tf, int ntaper, int nsig) {
+    std::vector<double> ws((size_t)2 * ntaper);
+    const double mid = 0.5 * (nsig - 1);
+    for (int k = 0; k < ntaper; ++k) {
+        double s0 = 0.0, s1 = 0.0;
+        for (int n = 0; n < nsig; ++n) { const double w = tf[(size_t)k * nsig + n]; s0 += w; s1 += w * (n - mid); }
+        ws[2 * k] = s0;
+        ws[2 * k + 1] = s1;
+    }
+    return ws;
+}
+
+// the windows times scale / 2 (mtmfft_quad_kernel: no scaling left in its epilogue)
+inline std::vector<float> taper_half_table(const double* tapers, size_t count, double scale) {
+    std::vector<float> th(count);
+    for (size_t i = 0; i < count; ++i) th[i] = (float)(tapers[i] * (0.5 * scale));
+    return th;
+}
+
+// frequency selection -> inverse map bin -> output slot (-1: bin not kept); *ident: every bin, in order.  A selection that
+// names a bin outside [0, nf) or twice is refused: empty map, the reason in *err
+inline std::vector<int> fpos_map(const int* freq_idx, int nfsel, int nf, bool* ident, std::string* err) {
+    std::vector<int> fpos(nf, -1);
+    char msg[96];
+    *ident = (nfsel == nf);
+    for (int i = 0; i < nfsel; ++i) {
+        const int f = freq_idx[i];
+        if (f < 0 || f >= nf) { std::snprintf(msg, sizeof msg, "freq_idx[%d]=%d outside [0,%d)", i, f, nf); *err = msg; return {}; }
+        if (fpos[f] >= 0) { std::snprintf(msg, sizeof msg, "freq_idx holds duplicate bin %d", f); *err = msg; return {}; }
+        fpos[f] = i;
+        *ident = *ident && (f == i);
+    }
+    return fpos;
 }
 }  // namespace spy

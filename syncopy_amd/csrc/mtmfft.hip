@@ -1,8 +1,8 @@
 // Host side of K1/K2: plan construction and kernel dispatch for the tapered-FFT
 // kernels (spyhip_fft_plan_create / spyhip_fft_exec of include/spyhip.h).
 //
-// mtmfft_route.h decides which kernel family serves a plan (pure integer logic); this file builds the tables the
-// family needs and launches it: one exec_* function per family.
+// mtmfft_route.h decides which kernel family serves a plan (pure integer logic) and mtmfft_tables.h builds the host tables
+// the family needs; this file uploads them and launches the family: one exec_* function per family.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -10,8 +10,7 @@
 #include <string>
 
 #include "spy_common.h"
-#include "host_fft.h"
-#include "mtmfft_route.h"
+#include "mtmfft_tables.h"    // mtmfft_route.h, host_fft.h
 #include "mtmfft_kernel.h"
 #include "mtmfft2_kernel.h"
 #include "mtmfft_blue_kernel.h"
@@ -120,23 +119,6 @@ struct spyhip_fft_plan {
 };
 
 namespace {
-
-using spy::twiddle_table;
-
-using spy::bluestein_tables;
-
-// [ntaper][2]: sum w_k, sum w_k (n - mid)
-std::vector<double> taper_moments(const std::vector<float>& tf, int ntaper, int nsig) {
-    std::vector<double> ws((size_t)2 * ntaper);
-    const double mid = 0.5 * (nsig - 1);
-    for (int k = 0; k < ntaper; ++k) {
-        double s0 = 0.0, s1 = 0.0;
-        for (int n = 0; n < nsig; ++n) { const double w = tf[(size_t)k * nsig + n]; s0 += w; s1 += w * (n - mid); }
-        ws[2 * k] = s0;
-        ws[2 * k + 1] = s1;
-    }
-    return ws;
-}
 
 int outk_of(const spyhip_fft_plan* p) { return spyfft::outk_of(p->output); }
 
@@ -473,11 +455,6 @@ extern "C" int spyhip_fft_plan_create(spyhip_ctx* ctx, int nsig, int nfft, int n
     std::vector<float> tf((size_t)ntaper * nsig);
     for (size_t i = 0; i < tf.size(); ++i) tf[i] = (float)tapers[i];
     if (p->tapers.upload(tf, s)) return -2;
-    if (r.family == Family::QUAD || r.family == Family::QUAD_HALF) {
-        std::vector<float> th(tf.size());
-        for (size_t i = 0; i < th.size(); ++i) th[i] = (float)(tapers[i] * (0.5 * scale));
-        if (p->tapers_half.upload(th, s)) return -2;
-    }
     {   // the windows as the reference holds them (float64), for spyhip_fft_plan_set_precision
         std::vector<double> td(tapers, tapers + (size_t)ntaper * nsig);
         if (p->tapers64.upload(td, s)) return -2;
@@ -487,59 +464,19 @@ extern "C" int spyhip_fft_plan_create(spyhip_ctx* ctx, int nsig, int nfft, int n
     p->identity_freq = (freq_idx == nullptr);
     p->nfsel = freq_idx ? nfsel : nf;
     if (freq_idx) {
-        std::vector<int> fpos(nf, -1);
-        bool ident = (nfsel == nf);
-        for (int i = 0; i < nfsel; ++i) {
-            const int f = freq_idx[i];
-            if (f < 0 || f >= nf) { spy::set_error("freq_idx[%d]=%d outside [0,%d)", i, f, nf); return -1; }
-            if (fpos[f] >= 0) { spy::set_error("freq_idx holds duplicate bin %d", f); return -1; }
-            fpos[f] = i;
-            ident = ident && (f == i);
-        }
-        p->identity_freq = ident;
-        if (!ident && p->fpos.upload(fpos, s)) return -2;
+        std::string err;
+        const std::vector<int> fpos = spy::fpos_map(freq_idx, nfsel, nf, &p->identity_freq, &err);
+        if (!err.empty()) { spy::set_error("%s", err.c_str()); return -1; }
+        if (!p->identity_freq && p->fpos.upload(fpos, s)) return -2;
     }
 
     if (r.err) { spy::set_error("%s", r.message.c_str()); return r.err; }
     p->kernel_name = r.kernel_name;
-    std::vector<float2> chirp, bhat;
-    switch (r.family) {
-        case Family::QUAD: case Family::DEC: case Family::MIXED:
-            if (p->tw.upload(twiddle_table<float2>(nfft), s)) return -2;
-            break;
-        case Family::QUAD_HALF: case Family::DEC_HALF:
-            if (p->tw.upload(twiddle_table<float2>(nfft / 2), s) || p->twh.upload(twiddle_table<float2>(nfft, nfft / 4 + 1), s)) return -2;
-            break;
-        case Family::BLUE:
-            bluestein_tables(nfft, r.M, 0, &chirp, &bhat);
-            if (p->chirp.upload(chirp, s) || p->bhat.upload(bhat, s) || p->tw.upload(twiddle_table<float2>(r.M), s)) return -2;
-            break;
-        case Family::DECLONG:
-            if (p->tw1.upload(twiddle_table<float2>(r.M), s) || p->tw2.upload(twiddle_table<float2>(r.P), s) ||
-                p->twM.upload(twiddle_table<float2>(nfft), s) || p->wsum.upload(taper_moments(tf, ntaper, nsig), s)) return -2;
-            break;
-        case Family::LONG:
-            bluestein_tables(nfft, r.M, 1 << r.l1, &chirp, &bhat);      // bhat in [k1][k2] order, 1/M folded in
-            if (p->chirp.upload(chirp, s) || p->bhat.upload(bhat, s) ||
-                p->tw1.upload(twiddle_table<float2>(1 << r.l1), s) || p->tw2.upload(twiddle_table<float2>(1 << r.l2), s) ||
-                p->twM.upload(twiddle_table<float2>(r.M), s) || p->wsum.upload(taper_moments(tf, ntaper, nsig), s)) return -2;
-            break;
-        case Family::GENERIC:
-            if (!r.direct) {
-                bluestein_tables(nfft, r.M, 0, &chirp, &bhat);
-                if (p->chirp.upload(chirp, s) || p->bhat.upload(bhat, s)) return -2;
-            }
-            if (p->tw.upload(twiddle_table<float2>(r.M), s)) return -2;
-            p->gen.n = r.M;
-            p->gen.nfac = r.nfac;
-            std::copy(r.radix, r.radix + spyfft::GEN_MAXFAC, p->gen.radix);
-            p->gen.nfft = nfft;
-            p->gen.bluestein = r.direct ? 0 : 1;
-            p->gen.chirp = p->chirp.p;
-            p->gen.bhat = p->bhat.p;
-            p->gen.stage_x = r.stage_x ? 1 : 0;
-            break;
-    }
+    const spyfft::FftTables<float2> t = spyfft::fft_tables<float2>(r, nfft, nsig, ntaper, tapers, scale, tf);
+    auto up = [s](auto& buf, const auto& v) { return !v.empty() && buf.upload(v, s); };      // (a table the family does not read stays unallocated)
+    if (up(p->tapers_half, t.tapers_half) || up(p->tw, t.tw) || up(p->twh, t.twh) || up(p->chirp, t.chirp) || up(p->bhat, t.bhat) ||
+        up(p->tw1, t.tw1) || up(p->tw2, t.tw2) || up(p->twM, t.twM) || up(p->wsum, t.wsum)) return -2;
+    if (r.family == Family::GENERIC) p->gen = spyfft::gen_plan<spyfft::GenPlan>(r, nfft, p->chirp.p, p->bhat.p);
     *out = p.release();
     return 0;
 }
@@ -590,16 +527,12 @@ extern "C" int spyhip_fft_plan_set_precision(spyhip_fft_plan* p, int reference) 
     const spyfft::Route64 r = spyfft::fft_route64(p->nfft, p->output, p->keeptapers, p->r);
     if (r.err) { spy::set_error("%s", r.message.c_str()); return r.err; }
     hipStream_t s = p->ctx->stream;
-    if (r.family == Family64::DEC64_HALF && !p->tw64h.p && p->tw64h.upload(twiddle_table<double2>(p->nfft / 2), s)) return -2;
-    // (DECLONG64 is chosen only with Family::DECLONG of the float32 route, whose taper moments `wsum` it shares)
-    if (r.family == Family64::DECLONG64 && !p->tw64_sub.p &&
-        (p->tw64_sub.upload(twiddle_table<double2>(r.M), s) || p->tw64_P.upload(twiddle_table<double2>(r.P), s))) return -2;
-    if (r.blue_M && !p->chirp64.p) {
-        std::vector<double2> chirp, bhat;
-        bluestein_tables(p->nfft, r.blue_M, 0, &chirp, &bhat);
-        if (p->chirp64.upload(chirp, s) || p->bhat64.upload(bhat, s)) return -2;
+    if (!p->tw64.p) {           // (the route is a function of the plan: its tables are built once; tw64 goes up last)
+        const spyfft::FftTables<double2> t = spyfft::fft_tables64<double2>(r, p->nfft);
+        auto up = [s](auto& buf, const auto& v) { return !buf.p && !v.empty() && buf.upload(v, s); };
+        if (up(p->tw64h, t.twh) || up(p->tw64_sub, t.tw1) || up(p->tw64_P, t.tw2) || up(p->chirp64, t.chirp) || up(p->bhat64, t.bhat) ||
+            up(p->tw64, t.tw)) return -2;
     }
-    if (!p->tw64.p && p->tw64.upload(twiddle_table<double2>(r.blue_M ? r.blue_M : p->nfft), s)) return -2;
     p->r64 = r;
     p->precision64 = true;
     p->kernel_name = r.kernel_name;

@@ -4,10 +4,10 @@
 namespace spyfft {
 int dec_launch_f(hipStream_t stream, const MtmArgs& a, int nfft, int nquads, int outk, bool mean) {
     switch (nfft) {
-        case 300: return dec_launch_mode<CfgD<10, 10, 1, 1, 8, 3>>(stream, a, nquads, outk, mean);
-        case 600: return dec_launch_mode<CfgD<10, 10, 2, 1, 4, 3>>(stream, a, nquads, outk, mean);
-        case 1500: return dec_launch_mode<CfgD<10, 10, 5, 1, 2, 3>>(stream, a, nquads, outk, mean);
-        case 3000: return dec_launch_mode<CfgD<10, 10, 10, 1, 1, 3>>(stream, a, nquads, outk, mean);
+        case 300: return dec_launch_mode<D_300>(stream, a, nquads, outk, mean);
+        case 600: return dec_launch_mode<D_600>(stream, a, nquads, outk, mean);
+        case 1500: return dec_launch_mode<D_1500>(stream, a, nquads, outk, mean);
+        case 3000: return dec_launch_mode<D_3000>(stream, a, nquads, outk, mean);
         default: return -100;
     }
 }

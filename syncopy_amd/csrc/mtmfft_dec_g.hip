@@ -4,8 +4,8 @@
 namespace spyfft {
 int dec_launch_g(hipStream_t stream, const MtmArgs& a, int nfft, int nquads, int outk, bool mean) {
     switch (nfft) {
-        case 6000: return dec_launch_mode<CfgD<10, 10, 10, 2, 1, 3>>(stream, a, nquads, outk, mean);
-        case 7500: return dec_launch_mode<CfgD<10, 10, 5, 5, 1, 3>>(stream, a, nquads, outk, mean);
+        case 6000: return dec_launch_mode<D_6000>(stream, a, nquads, outk, mean);
+        case 7500: return dec_launch_mode<D_7500>(stream, a, nquads, outk, mean);
         default: return -100;
     }
 }

@@ -7,7 +7,7 @@
 namespace spyfft {
 int dec_launch_h(hipStream_t stream, const MtmArgs& a, int nfft, int nquads, int outk, bool mean) {
     switch (nfft) {
-        case 10000: return dec_launch_mode<CfgD<20, 20, 5, 5, 1, 1, true>>(stream, a, nquads, outk, mean);
+        case 10000: return dec_launch_mode<D_10000>(stream, a, nquads, outk, mean);
         default: return -100;
     }
 }

@@ -5,10 +5,10 @@
 namespace spyfft {
 int dec_launch_i(hipStream_t stream, const MtmArgs& a, int nfft, int nquads, int outk, bool mean) {
     switch (nfft) {
-        case 768: return dec_launch_mode<CfgD<16, 16, 1, 1, 4, 3>>(stream, a, nquads, outk, mean);
-        case 1536: return dec_launch_mode<CfgD<16, 16, 2, 1, 2, 3>>(stream, a, nquads, outk, mean);
-        case 3072: return dec_launch_mode<CfgD<16, 16, 4, 1, 1, 3>>(stream, a, nquads, outk, mean);
-        case 6144: return dec_launch_mode<CfgD<16, 16, 8, 1, 1, 3>>(stream, a, nquads, outk, mean);
+        case 768: return dec_launch_mode<D_768>(stream, a, nquads, outk, mean);
+        case 1536: return dec_launch_mode<D_1536>(stream, a, nquads, outk, mean);
+        case 3072: return dec_launch_mode<D_3072>(stream, a, nquads, outk, mean);
+        case 6144: return dec_launch_mode<D_6144>(stream, a, nquads, outk, mean);
         default: return -100;
     }
 }

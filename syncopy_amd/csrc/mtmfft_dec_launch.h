@@ -1,7 +1,7 @@
 // Launch plumbing shared by the translation units of the decimal-length kernel (mtmfft_dec_kernel.h)
 #pragma once
 #include "spy_common.h"
-#include "mtmfft_dec_kernel.h"
+#include "mtmfft_dec_cfg.h"     // mtmfft_dec_kernel.h + the named schedules
 
 namespace spyfft {
 

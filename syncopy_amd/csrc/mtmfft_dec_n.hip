@@ -5,8 +5,8 @@
 namespace spyfft {
 int dec_launch_half_b(hipStream_t stream, const MtmArgs& a, int nfft, int npairs, int outk, bool mean) {
     switch (nfft) {
-        case 16000: return dec_launch_mode<CfgD<20, 20, 20, 1, 1, 1, false, true>>(stream, a, npairs, outk, mean);
-        case 20000: return dec_launch_mode<CfgD<20, 20, 5, 5, 1, 1, true, true>>(stream, a, npairs, outk, mean);
+        case 16000: return dec_launch_mode<DH_16000>(stream, a, npairs, outk, mean);
+        case 20000: return dec_launch_mode<DH_20000>(stream, a, npairs, outk, mean);
         default: return -100;
     }
 }

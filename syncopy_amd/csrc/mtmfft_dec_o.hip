@@ -5,8 +5,8 @@
 namespace spyfft {
 int dec_launch_half_c(hipStream_t stream, const MtmArgs& a, int nfft, int npairs, int outk, bool mean) {
     switch (nfft) {
-        case 10000: return dec_launch_mode<CfgD<10, 10, 10, 5, 1, 1, false, true>>(stream, a, npairs, outk, mean);
-        case 5000: return dec_launch_mode<CfgD<10, 10, 5, 5, 1, 1, false, true>>(stream, a, npairs, outk, mean);
+        case 10000: return dec_launch_mode<DH_10000>(stream, a, npairs, outk, mean);
+        case 5000: return dec_launch_mode<DH_5000>(stream, a, npairs, outk, mean);
         default: return -100;
     }
 }

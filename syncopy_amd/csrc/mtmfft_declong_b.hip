@@ -1,6 +1,7 @@
 // declong_sub_kernel instances (mtmfft_declong.h): sub-transform lengths 4000, 8000, 10000 (20 values per thread)
 #include "spy_common.h"
 #include "mtmfft_declong.h"
+#include "mtmfft_dec_cfg.h"
 
 namespace spyfft {
 
@@ -17,9 +18,9 @@ static int declong_sub(hipStream_t stream, const LongArgs& a, int P, long long n
 
 int declong_launch_sub_b(hipStream_t stream, const LongArgs& a, int M, int P, long long nblocks) {
     switch (M) {
-        case 4000: return declong_sub<CfgD<20, 20, 10, 1, 1>>(stream, a, P, nblocks);
-        case 8000: return declong_sub<CfgD<20, 20, 20, 1, 1>>(stream, a, P, nblocks);
-        case 10000: return declong_sub<CfgD<20, 20, 5, 5, 1, 1, true>>(stream, a, P, nblocks);
+        case 4000: return declong_sub<D_4000>(stream, a, P, nblocks);
+        case 8000: return declong_sub<D_8000>(stream, a, P, nblocks);
+        case 10000: return declong_sub<D_10000>(stream, a, P, nblocks);
         default: return -100;
     }
 }

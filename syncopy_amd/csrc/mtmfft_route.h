@@ -1,5 +1,7 @@
 // Which kernel family serves a tapered FFT (K1): pure integer logic, no HIP header and no runtime call, so that the
-// selection is testable on any host (tests/test_fft_route.py).  mtmfft.hip builds the tables a route needs and launches it.
+// selection is testable on any host (tests/test_fft_route.py).  Two readers: mtmfft.hip uploads the tables a route needs
+// (mtmfft_tables.h) and launches it; the CPU kernel emulator of the tests (tests/emu/emu_kernels.cpp: emu_fft_exec) asks the
+// same route, points its arguments at the same tables and walks the same steps on host memory.
 //
 // The length tables below are the only place the host code asks "is this length scheduled"; the instance translation
 // units (mtmfft_dec_*.hip, mtmfft_dec64_*.hip) hold the matching `case`s, and tests/test_gpu_fft_schedules.py runs every
@@ -112,92 +114,91 @@ std::string fmt(const char* f, A... a) {
 
 }  // namespace route_detail
 
-// The float32 route.  The order of the tests is the order of precedence between the families.
-inline Route fft_route(int nsig, int nfft, int nchan, int ntaper, int output, int keeptapers, size_t lds_per_block,
-                       bool force_generic) {
+// "OUTK, MEAN" as the kernel names spell the output mode
+inline std::string route_mode(int output, int keeptapers) {
+    return route_detail::fmt("%d, %s", outk_of(output), keeptapers ? "false" : "true");
+}
+
+// ---- One filler per family: the parameters that family launches by, and its kernel name.  fft_route() below calls them in
+// the order of precedence; the kernel emulator of the tests calls one directly to run a family on a shape the route gives
+// to another (LONG at 1500 samples, BLUE instead of MIXED at 500, DECLONG at 6 x 2000).
+
+// QUAD: power-of-two nfft in 256 ... 8192 on the packed engine; QUAD_HALF: 2^14 as channel pairs through the 8192-point
+// schedule (mtmfft_quad_half.hip)
+inline void route_quad(Route& r, int nfft, int output, int keeptapers) {
     using namespace route_detail;
-    (void)ntaper;               // (reserved: no family depends on the taper count today)
-    Route r;
-    const bool tuned = !force_generic;
-    const std::string mode = fmt("%d, %s", outk_of(output), keeptapers ? "false" : "true");
-    if (tuned && pow2(nfft) && nfft >= 256 && nfft <= 16384) {
-        r.log2n = ilog2(nfft);
-        if (r.log2n == 14) {        // 2^14: channel pairs through the 8192-point schedule (mtmfft_quad_half.hip)
-            r.family = Family::QUAD_HALF;
-            r.kernel_name = fmt("mtmfft_quad_kernel<13, 1, %s, HALF of N = %d>", mode.c_str(), nfft);
-            return r;
-        }
-        r.family = Family::QUAD;
-        r.G = default_G(r.log2n);
-        // complex spectra of every taper at N = 4096 are store-bound: two quads per workgroup (one workgroup per
-        // CU) write 64 contiguous bytes per bin row and are 13 % faster; everything else prefers two independent
-        // 256-thread workgroups per CU
-        if (r.log2n == 12 && outk_of(output) == 2 && keeptapers) r.G = 2;
-        r.kernel_name = fmt("mtmfft_quad_kernel<%d, %d, %s>", r.log2n, r.G, mode.c_str());
-        return r;
+    const std::string mode = route_mode(output, keeptapers);
+    r.log2n = ilog2(nfft);
+    if (r.log2n == 14) {
+        r.family = Family::QUAD_HALF;
+        r.kernel_name = fmt("mtmfft_quad_kernel<13, 1, %s, HALF of N = %d>", mode.c_str(), nfft);
+        return;
     }
-    if (tuned && in_table(DEC_LENGTHS, nfft)) {
-        // decimal trial lengths: radix schedules fixed at compile time, 10 values per thread.
-        // HALF form where it measured faster than the quad form (tools/half_probe.py): 5000 (88 KB of LDS per quad: one
-        // workgroup per CU; pairs 12.8 vs 16.0 us/trial at 256 channels) and 10000 with the taper mean (split exchanges
-        // in quad form: 39.3 vs 43.9, complex 42.6 vs 61.7; with every taper kept the 8-byte stores of a pair cost more)
-        const bool half = nfft == 5000 || (nfft == 10000 && !keeptapers);
-        r.family = half ? Family::DEC_HALF : Family::DEC;
-        r.kernel_name = fmt(half ? "mtmfft_dec_kernel<HALF of N = %d, %s>" : "mtmfft_dec_kernel<N = %d, %s>", nfft, mode.c_str());
-        return r;
-    }
-    // 5-smooth lengths take the mixed-radix engine whatever the taper count: the chirp-z kernel's two length-M transforms
-    // and three pointwise products leave ~4x the float32 error of a direct transform
-    if (tuned && mix_schedule(nfft, (nchan + 3) / 4, &r.mix, &r.mix_threads, &r.lds_bytes) && r.lds_bytes <= lds_per_block) {
-        r.family = Family::MIXED;
-        r.G = 1 << r.mix.lg;
-        std::string sched;
-        for (int i = 0; i < r.mix.npass; ++i) sched += (i ? "x" : "") + std::to_string(r.mix.radix[i]);
-        r.kernel_name = fmt("mtmfft_mixed_kernel<%s> N=%d (%s) %d threads x %d quads", mode.c_str(), nfft, sched.c_str(),
-                            r.mix.th, r.G);
-        return r;
-    }
-    if (tuned && nfft >= 2 && 2 * nfft - 1 <= 8192) {
-        // Bluestein on the packed power-of-two engine: M = 2^log2n >= 2 nfft - 1 (at least 256)
-        r.family = Family::BLUE;
-        r.M = 256;
-        while (r.M < 2 * nfft - 1) r.M <<= 1;
-        r.log2n = ilog2(r.M);
-        r.G = default_G(r.log2n);
-        r.kernel_name = fmt("mtmfft_blue_kernel<%d, %d, %s>", r.log2n, r.G, mode.c_str());
-        return r;
-    }
-    if (tuned && nfft > 10240 && declong_split(nfft, &r.P, &r.M)) {
-        if (in_table(HALF_LENGTHS, nfft)) {
-            // up to 20480 samples a channel PAIR still fits one workgroup's LDS: the real transform through the schedule
-            // of nfft / 2 (CfgD::HALF)
-            r.family = Family::DEC_HALF;
-            r.P = r.M = 0;
-            r.kernel_name = fmt("mtmfft_dec_kernel<HALF of N = %d, %s>", nfft, mode.c_str());
-            return r;
-        }
-        // longer than one workgroup's LDS, N = P M with M a scheduled length: decimation in time through HBM
-        r.family = Family::DECLONG;
-        r.kernel_name = fmt("declong<%d x %d, %s>", r.P, r.M, mode.c_str());
-        return r;
-    }
-    // (lengths up to 10240 with prime factors <= 13 stay on the generic LDS kernel below: measured 10-20 % faster than the
-    // HBM round trips of the long path; everything longer, and awkward lengths, go there)
-    if (tuned && nfft <= (1 << 19) && !(nfft <= 10240 && factorize(nfft, r.radix, &r.nfac))) {
-        // Bluestein with four-step transforms through HBM: M = 2^m >= 2 nfft - 1 (>= 4096), M1 = 2^ceil(m/2), M2 = M / M1;
-        // a power-of-two nfft is one plain four-step transform
-        r.family = Family::LONG;
-        r.direct = pow2(nfft) && nfft >= 4096;
-        int m = 12;
-        while ((1LL << m) < (r.direct ? (long long)nfft : 2LL * nfft - 1)) ++m;
-        r.M = 1 << m;
-        r.l1 = (m + 1) / 2;
-        r.l2 = m / 2;
-        r.kernel_name = fmt("mtmfft_long<%d x %d, %s>", 1 << r.l1, 1 << r.l2, mode.c_str());
-        return r;
-    }
+    r.family = Family::QUAD;
+    r.G = default_G(r.log2n);
+    // complex spectra of every taper at N = 4096 are store-bound: two quads per workgroup (one workgroup per
+    // CU) write 64 contiguous bytes per bin row and are 13 % faster; everything else prefers two independent
+    // 256-thread workgroups per CU
+    if (r.log2n == 12 && outk_of(output) == 2 && keeptapers) r.G = 2;
+    r.kernel_name = fmt("mtmfft_quad_kernel<%d, %d, %s>", r.log2n, r.G, mode.c_str());
+}
+
+// DEC / DEC_HALF: the compile-time schedule of nfft (HALF: channel pairs through the schedule of nfft / 2)
+inline void route_dec(Route& r, int nfft, bool half, const std::string& mode) {
+    r.family = half ? Family::DEC_HALF : Family::DEC;
+    r.kernel_name = route_detail::fmt(half ? "mtmfft_dec_kernel<HALF of N = %d, %s>" : "mtmfft_dec_kernel<N = %d, %s>", nfft, mode.c_str());
+}
+
+// MIXED: the packed mixed-radix engine, if it has a schedule for nfft that fits the LDS
+inline bool route_mixed(Route& r, int nfft, int nchan, size_t lds_per_block, const std::string& mode) {
+    if (!mix_schedule(nfft, (nchan + 3) / 4, &r.mix, &r.mix_threads, &r.lds_bytes) || r.lds_bytes > lds_per_block) return false;
+    r.family = Family::MIXED;
+    r.G = 1 << r.mix.lg;
+    std::string sched;
+    for (int i = 0; i < r.mix.npass; ++i) sched += (i ? "x" : "") + std::to_string(r.mix.radix[i]);
+    r.kernel_name = route_detail::fmt("mtmfft_mixed_kernel<%s> N=%d (%s) %d threads x %d quads", mode.c_str(), nfft, sched.c_str(),
+                                      r.mix.th, r.G);
+    return true;
+}
+
+// BLUE: Bluestein on the packed power-of-two engine: M = 2^log2n >= 2 nfft - 1 (at least 256, at most 8192)
+inline void route_blue(Route& r, int nfft, const std::string& mode) {
+    using namespace route_detail;
+    r.family = Family::BLUE;
+    r.M = 256;
+    while (r.M < 2 * nfft - 1) r.M <<= 1;
+    r.log2n = ilog2(r.M);
+    r.G = default_G(r.log2n);
+    r.kernel_name = fmt("mtmfft_blue_kernel<%d, %d, %s>", r.log2n, r.G, mode.c_str());
+}
+
+// DECLONG: longer than one workgroup's LDS, N = P M with M a scheduled length: decimation in time through HBM
+inline bool route_declong(Route& r, int nfft, const std::string& mode) {
+    if (!route_detail::declong_split(nfft, &r.P, &r.M)) return false;
+    r.family = Family::DECLONG;
+    r.kernel_name = route_detail::fmt("declong<%d x %d, %s>", r.P, r.M, mode.c_str());
+    return true;
+}
+
+// LONG: Bluestein with four-step transforms through HBM: M = 2^m >= 2 nfft - 1 (>= 4096), M1 = 2^ceil(m/2), M2 = M / M1;
+// a power-of-two nfft is one plain four-step transform
+inline void route_long(Route& r, int nfft, const std::string& mode) {
+    using namespace route_detail;
+    r.family = Family::LONG;
+    r.direct = pow2(nfft) && nfft >= 4096;
+    int m = 12;
+    while ((1LL << m) < (r.direct ? (long long)nfft : 2LL * nfft - 1)) ++m;
+    r.M = 1 << m;
+    r.l1 = (m + 1) / 2;
+    r.l2 = m / 2;
+    r.kernel_name = fmt("mtmfft_long<%d x %d, %s>", 1 << r.l1, 1 << r.l2, mode.c_str());
+}
+
+// GENERIC: Stockham passes in LDS over the radix list of nfft, or of the Bluestein length where nfft has a prime factor > 13
+inline void route_generic(Route& r, int nsig, int nfft, size_t lds_per_block, const std::string& mode) {
+    using namespace route_detail;
     r.family = Family::GENERIC;
-    if (nfft < 16) { r.err = -1; r.message = fmt("nfft=%d too short (need >= 16)", nfft); return r; }
+    if (nfft < 16) { r.err = -1; r.message = fmt("nfft=%d too short (need >= 16)", nfft); return; }
     r.M = nfft;
     r.direct = factorize(nfft, r.radix, &r.nfac);
     if (!r.direct) {            // Bluestein: circular convolution of length M = pow2 >= 2*nfft-1
@@ -211,10 +212,49 @@ inline Route fft_route(int nsig, int nfft, int nchan, int ntaper, int output, in
     if (r.lds_bytes > lds_per_block) {
         r.err = -3;
         r.message = fmt("nfft=%d needs %zu bytes of LDS (> %zu): unsupported length", nfft, r.lds_bytes, lds_per_block);
-        return r;
+        return;
     }
     r.kernel_name = fmt("mtmfft_generic_kernel<%s>", mode.c_str());
+}
+
+// The float32 route.  The order of the tests is the order of precedence between the families.
+inline Route fft_route(int nsig, int nfft, int nchan, int ntaper, int output, int keeptapers, size_t lds_per_block,
+                       bool force_generic) {
+    using namespace route_detail;
+    (void)ntaper;               // (reserved: no family depends on the taper count today)
+    Route r;
+    const std::string mode = route_mode(output, keeptapers);
+    if (force_generic) { route_generic(r, nsig, nfft, lds_per_block, mode); return r; }
+    if (pow2(nfft) && nfft >= 256 && nfft <= 16384) { route_quad(r, nfft, output, keeptapers); return r; }
+    if (in_table(DEC_LENGTHS, nfft)) {
+        // decimal trial lengths: radix schedules fixed at compile time, 10 values per thread.
+        // HALF form where it measured faster than the quad form (tools/half_probe.py): 5000 (88 KB of LDS per quad: one
+        // workgroup per CU; pairs 12.8 vs 16.0 us/trial at 256 channels) and 10000 with the taper mean (split exchanges
+        // in quad form: 39.3 vs 43.9, complex 42.6 vs 61.7; with every taper kept the 8-byte stores of a pair cost more)
+        route_dec(r, nfft, nfft == 5000 || (nfft == 10000 && !keeptapers), mode);
+        return r;
+    }
+    // 5-smooth lengths take the mixed-radix engine whatever the taper count: the chirp-z kernel's two length-M transforms
+    // and three pointwise products leave ~4x the float32 error of a direct transform
+    if (route_mixed(r, nfft, nchan, lds_per_block, mode)) return r;
+    if (nfft >= 2 && 2 * nfft - 1 <= 8192) { route_blue(r, nfft, mode); return r; }
+    if (nfft > 10240 && route_declong(r, nfft, mode)) {
+        // up to 20480 samples a channel PAIR still fits one workgroup's LDS: the real transform through the schedule
+        // of nfft / 2 (CfgD::HALF)
+        if (in_table(HALF_LENGTHS, nfft)) { r.P = r.M = 0; route_dec(r, nfft, true, mode); }
+        return r;
+    }
+    // (lengths up to 10240 with prime factors <= 13 stay on the generic LDS kernel below: measured 10-20 % faster than the
+    // HBM round trips of the long path; everything longer, and awkward lengths, go there)
+    if (nfft <= (1 << 19) && !(nfft <= 10240 && factorize(nfft, r.radix, &r.nfac))) { route_long(r, nfft, mode); return r; }
+    route_generic(r, nsig, nfft, lds_per_block, mode);
     return r;
+}
+
+// DEC64 / DEC64_HALF: the reference-precision compile-time schedule of nfft (filler, as the float32 ones above)
+inline void route64_dec(Route64& r, int nfft, bool half, const std::string& mode) {
+    r.family = half ? Family64::DEC64_HALF : Family64::DEC64;
+    r.kernel_name = route_detail::fmt(half ? "mtmfft_dec64_kernel<HALF of N = %d, %s>" : "mtmfft_dec64_kernel<N = %d, %s>", nfft, mode.c_str());
 }
 
 // The reference-precision route (spyhip_fft_plan_set_precision): float64 taper product and transform.  `f32` is the
@@ -223,17 +263,10 @@ inline Route fft_route(int nsig, int nfft, int nchan, int ntaper, int output, in
 inline Route64 fft_route64(int nfft, int output, int keeptapers, const Route& f32) {
     using namespace route_detail;
     Route64 r;
-    const std::string mode = fmt("%d, %s", outk_of(output), keeptapers ? "false" : "true");
-    if (in_table(HALF_LENGTHS, nfft)) {
-        r.family = Family64::DEC64_HALF;       // single channels through the schedule of nfft / 2 (CfgD64::HALF)
-        r.kernel_name = fmt("mtmfft_dec64_kernel<HALF of N = %d, %s>", nfft, mode.c_str());
-        return r;
-    }
-    if (in_table(DEC64_LENGTHS, nfft)) {
-        r.family = Family64::DEC64;
-        r.kernel_name = fmt("mtmfft_dec64_kernel<N = %d, %s>", nfft, mode.c_str());
-        return r;
-    }
+    const std::string mode = route_mode(output, keeptapers);
+    // (HALF: single channels through the schedule of nfft / 2, CfgD64::HALF)
+    if (in_table(HALF_LENGTHS, nfft)) { route64_dec(r, nfft, true, mode); return r; }
+    if (in_table(DEC64_LENGTHS, nfft)) { route64_dec(r, nfft, false, mode); return r; }
     if (f32.family == Family::DECLONG) {
         r.family = Family64::DECLONG64;
         r.P = f32.P;

@@ -1,8 +1,9 @@
 """ctypes front end of the CPU emulation of the HIP kernels (TEST INFRASTRUCTURE ONLY).
 
-Mirrors the plan construction of syncopy_amd/csrc/mtmfft.hip in NumPy so that a
-test can run one kernel configuration on host arrays and compare it with the
-oracle.  Never imported by the package.
+Marshals host arrays into the entries of tests/emu/emu_kernels.cpp so that a test
+can run one kernel configuration and compare it with the oracle.  Routes, tables
+and launch geometry are the library's own headers on the C side; none of them is
+restated here.  Never imported by the package.
 """
 import ctypes as C
 import os
@@ -27,329 +28,123 @@ def _p(a, typ):
     return None if a is None else a.ctypes.data_as(C.POINTER(typ))
 
 
-def twiddles(n):
-    m = np.arange(n, dtype=np.float64)
-    ang = -2.0 * np.pi * m / n
-    return np.stack([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32).copy()
-
-
-def factorize(n):
-    rad = []
-    for c in (16, 8, 4, 2, 3, 5, 7, 11, 13):
-        while n % c == 0 and n > 1:
-            rad.append(c)
-            n //= c
-    return rad, n == 1
-
-
 OUT_KINDS = {"pow": 0, "abs": 1, "fourier": 2, "complex": 2, "real": 3, "imag": 4, "angle": 5,
              "absreal": 6, "absimag": 7}
 
-
-def fft_exec(data, seg_start, seg_lo, seg_hi, nsig, nfft, tapers, scale, detrend=-1, demean_taper=False,
-             freq_idx=None, output="pow", keeptapers=True, chan_idx=None, G=None, force_generic=False, blocked=False,
-             force_long=False, reference_mean=False, no_mixed=False, mixed_nostage=False, dec=None):
-    """`reference_mean`: constant detrending with the means of seq_mean_kernel (spyhip_fft_plan_set_reference_mean).
-    `dec`: id of a compile-time schedule of mtmfft_dec_kernel (emu_kernels.cpp)."""
-    if reference_mean and detrend == 0:
-        d32 = np.ascontiguousarray(data, dtype=np.float32)
-        nch = d32.shape[1] if chan_idx is None else len(chan_idx)
-        means = seq_mean(d32, seg_start, seg_lo, seg_hi, nsig, chan_idx)
-        assert means.shape == (len(seg_start), nch)
-        lib().emu_set_means(_p(means, C.c_float))
-        try:
-            return fft_exec(d32, seg_start, seg_lo, seg_hi, nsig, nfft, tapers, scale, detrend, demean_taper, freq_idx,
-                            output, keeptapers, chan_idx, G, force_generic, blocked, force_long, False, no_mixed,
-                            mixed_nostage, dec)
-        finally:
-            lib().emu_set_means(None)
-    return _fft_exec(data, seg_start, seg_lo, seg_hi, nsig, nfft, tapers, scale, detrend, demean_taper, freq_idx,
-                     output, keeptapers, chan_idx, G, force_generic, blocked, force_long, no_mixed, mixed_nostage, dec)
+# `force` of emu_fft_exec (emu_kernels.cpp: enum Force): the filler of one family in place of the route's choice
+FORCE = {"route": 0, "generic": 1, "long": 2, "blue": 3, "mixed": 4, "declong": 5, "dec": 6,
+         "dec64": 7, "half64": 8, "plain64": 9}
+NO_INSTANCE = -100     # the route chose a kernel the emulator holds no instance of
+LAST_KERNEL = ""       # kernel_name of the route the last call ran (spyhip_fft_plan_kernel_name)
+LAST_MIXED = {}        # the schedule of the last call that ran the mixed-radix engine
 
 
-def seq_mean(data, seg_start, seg_lo, seg_hi, nsig, chan_idx=None):
-    """Emulated seq_mean_kernel: (nseg, nchan) float32 means in the reference's summation order."""
+def _segments(data, seg_start, seg_lo, seg_hi, chan_idx):
+    """The exec arguments of spyhip_fft_exec on host arrays: data, ld, nchan, chan_idx, seg_start, seg_lo, seg_hi."""
     data = np.ascontiguousarray(data, dtype=np.float32)
     ci = None if chan_idx is None else np.ascontiguousarray(chan_idx, dtype=np.int32)
     nchan = data.shape[1] if ci is None else len(ci)
-    ss = np.ascontiguousarray(seg_start, dtype=np.int64)
-    sl = np.ascontiguousarray(seg_lo, dtype=np.int64)
-    sh = np.ascontiguousarray(seg_hi, dtype=np.int64)
-    means = np.full((len(ss), nchan), np.nan, dtype=np.float32)
-    lib().emu_seq_mean(_p(data, C.c_float), C.c_longlong(data.shape[1]), _p(ci, C.c_int), _p(ss, C.c_longlong),
-                       _p(sl, C.c_longlong), _p(sh, C.c_longlong), C.c_int(len(ss)), C.c_int(nsig), C.c_int(nchan),
-                       _p(means, C.c_float))
-    return means
+    return (data, data.shape[1], nchan, ci, np.ascontiguousarray(seg_start, dtype=np.int64),
+            np.ascontiguousarray(seg_lo, dtype=np.int64), np.ascontiguousarray(seg_hi, dtype=np.int64))
 
 
-def twiddles64(n):
-    ang = -2.0 * np.pi * np.arange(n, dtype=np.float64) / n
-    return np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang)], axis=1))
-
-
-def fft_exec_f64(data, seg_start, seg_lo, seg_hi, nsig, nfft, tapers, scale, detrend=-1, demean_taper=False,
-                 freq_idx=None, output="pow", keeptapers=True, chan_idx=None, reference_mean=False, seg_f64=False,
-                 dec=True, bluestein=False, emu_id=None):
-    """Emulated spyhip_fft_exec of a plan with spyhip_fft_plan_set_precision(plan, 1): `dec` - the compile-time
-    schedule of mtmfft_dec64_kernel for this nfft; otherwise the any-length kernel, `bluestein` in its chirp-z form
-    (tables as spyhip_fft_plan_set_precision builds them).  dec="half": the HALF form (single channels through the
-    schedule of nfft / 2); `emu_id` picks a schedule variant of the emulator that shares its nfft with another (2002)."""
-    data = np.ascontiguousarray(data, dtype=np.float32)
-    ld = data.shape[1]
-    nchan = ld if chan_idx is None else len(chan_idx)
-    ci = None if chan_idx is None else np.ascontiguousarray(chan_idx, dtype=np.int32)
-    ss = np.ascontiguousarray(seg_start, dtype=np.int64)
-    sl = np.ascontiguousarray(seg_lo, dtype=np.int64)
-    sh = np.ascontiguousarray(seg_hi, dtype=np.int64)
+def _exec(data, seg_start, seg_lo, seg_hi, nsig, nfft, tapers, scale, detrend, demean_taper, freq_idx, output, keeptapers,
+          chan_idx, precision64=False, ref_mean=0, blocked=False, force="route", variant=0, nostage=False):
+    """emu_fft_exec: an emulated spyhip_fft_plan_create + options + spyhip_fft_exec.  The C side asks the library's route,
+    builds the library's tables and walks the library's steps; nothing about the plan is decided or built here."""
+    global LAST_KERNEL
+    data, ld, nchan, ci, ss, sl, sh = _segments(data, seg_start, seg_lo, seg_hi, chan_idx)
     nseg, K = len(ss), tapers.shape[0]
     tp = np.ascontiguousarray(tapers, dtype=np.float64)
-    nf = nfft // 2 + 1
-    if freq_idx is None:
-        fpos, nfsel = None, nf
-    else:
-        fi = np.asarray(freq_idx, dtype=np.int64)
-        nfsel = len(fi)
-        fpos = np.full(nf, -1, dtype=np.int32)
-        fpos[fi] = np.arange(nfsel, dtype=np.int32)
-    kind = OUT_KINDS[output]
-    out = np.full((nseg, K if keeptapers else 1, nfsel, nchan), np.nan, dtype=np.complex64 if kind == 2 else np.float32)
-    M, chirp, bhat = 0, None, None
-    if bluestein:
-        M = 16
-        while M < 2 * nfft - 1:
-            M *= 2
-        n = np.arange(nfft, dtype=np.int64)
-        ang = np.pi * ((n * n) % (2 * nfft)).astype(np.float64) / nfft
-        chirp = np.ascontiguousarray(np.stack([np.cos(ang), -np.sin(ang)], axis=1))
-        b = np.zeros(M, dtype=np.complex128)
-        b[:nfft] = np.cos(ang) + 1j * np.sin(ang)
-        b[M - n[1:]] = b[n[1:]]
-        B = np.fft.fft(b) / M
-        bhat = np.ascontiguousarray(np.stack([B.real, B.imag], axis=1))
-    means = None
-    if reference_mean and detrend == 0:
-        means = seq_mean(data, ss, sl, sh, nsig, chan_idx)
-        lib().emu_set_means(_p(means, C.c_float))
-    try:
-        rc = lib().emu_mtmfft_f64(
-            C.c_int(nfft if emu_id is None else emu_id), C.c_int(M), _p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int), _p(ss, C.c_longlong),
-            _p(sl, C.c_longlong), _p(sh, C.c_longlong), C.c_int(nseg), C.c_int(nsig), C.c_int(nchan), C.c_int(K),
-            _p(tp, C.c_double), _p(twiddles64(M if bluestein else nfft), C.c_double), _p(chirp, C.c_double),
-            _p(bhat, C.c_double), C.c_float(scale), C.c_int(detrend), C.c_int(int(demean_taper)), C.c_int(int(seg_f64)),
-            _p(fpos, C.c_int), C.c_int(nfsel), C.c_int(kind), C.c_int(int(keeptapers)),
-            C.c_int(2 if (dec == "half") else int(bool(dec) and not bluestein)),
-            out.ctypes.data_as(C.c_void_p))
-    finally:
-        lib().emu_set_means(None)
-    assert rc == 0, f"no emulated reference-precision kernel for nfft={nfft} (rc={rc})"
-    return out
-
-
-LAST_MIXED = {}
-
-
-def _fft_exec(data, seg_start, seg_lo, seg_hi, nsig, nfft, tapers, scale, detrend=-1, demean_taper=False,
-              freq_idx=None, output="pow", keeptapers=True, chan_idx=None, G=None, force_generic=False, blocked=False,
-              force_long=False, no_mixed=False, mixed_nostage=False, dec=None):
-    """Emulated spyhip_fft_exec.  data: (rows, ld) float32; tapers: (K, nsig) float64.
-    blocked: channel-blocked hand-over layout (nseg*K, ceil(nchan/4), nfsel, 4) (fourier, keeptapers)."""
-    data = np.ascontiguousarray(data, dtype=np.float32)
-    ld = data.shape[1]
-    nchan = ld if chan_idx is None else len(chan_idx)
-    ci = None if chan_idx is None else np.ascontiguousarray(chan_idx, dtype=np.int32)
-    ss = np.ascontiguousarray(seg_start, dtype=np.int64)
-    sl = np.ascontiguousarray(seg_lo, dtype=np.int64)
-    sh = np.ascontiguousarray(seg_hi, dtype=np.int64)
-    nseg = len(ss)
-    K = tapers.shape[0]
-    tp = np.ascontiguousarray(tapers, dtype=np.float32)
-    nf = nfft // 2 + 1
-    if freq_idx is None:
-        fpos, nfsel = None, nf
-    else:
-        fi = np.asarray(freq_idx, dtype=np.int64)
-        nfsel = len(fi)
-        fpos = np.full(nf, -1, dtype=np.int32)
-        fpos[fi] = np.arange(nfsel, dtype=np.int32)
+    fi = None if freq_idx is None else np.ascontiguousarray(freq_idx, dtype=np.int32)
+    nfsel = nfft // 2 + 1 if fi is None else len(fi)
     kind = OUT_KINDS[output]
     kout = K if keeptapers else 1
     out = np.full((nseg, kout, nfsel, nchan), np.nan, dtype=np.complex64 if kind == 2 else np.float32)
     if blocked:
         assert kind == 2 and keeptapers
         out = np.full((nseg * kout, (nchan + 3) // 4, nfsel, 4), np.nan, dtype=np.complex64)
-    if dec is not None:
-        # mtmfft_dec_kernel: the compile-time schedule `dec` (emu_kernels.cpp: emu_mtmfft_dec); dec < 0: the HALF form of
-        # nfft = -dec (channel pairs through the schedule of nfft / 2: twiddles of nfft / 2 + the half-step table)
-        half = int(dec) < 0
-        twh = np.ascontiguousarray(twiddles(nfft)[: nfft // 4 + 1]) if half else None
-        lib().emu_set_twh(_p(twh, C.c_float))
-        rc = lib().emu_mtmfft_dec(
-            C.c_int(int(dec)), _p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int),
-            _p(ss, C.c_longlong), _p(sl, C.c_longlong), _p(sh, C.c_longlong), C.c_int(nseg),
-            C.c_int(nsig), C.c_int(nchan), C.c_int(K), _p(tp, C.c_float), _p(twiddles(nfft // 2 if half else nfft), C.c_float),
-            C.c_float(scale), C.c_int(detrend), C.c_int(int(demean_taper)), _p(fpos, C.c_int),
-            C.c_int(nfsel), C.c_int(kind), C.c_int(int(keeptapers)), out.ctypes.data_as(C.c_void_p))
-        lib().emu_set_twh(None)
-        assert rc == 0, f"no emulated decimal kernel {dec}"
-        return out
-    pow2 = (nfft & (nfft - 1)) == 0 and 256 <= nfft <= 16384 and not force_generic
-    if pow2:
-        log2n = int(np.log2(nfft))
-        if G is None:
-            G = {8: 16, 9: 8, 10: 4, 11: 2, 12: 1, 13: 1, 14: 1}[log2n]
-            if log2n == 12 and kind == 2 and keeptapers:
-                G = 2               # as spyhip_fft_plan_create: store-bound complex spectra take two quads per workgroup
-        # 2^14 (as spyhip_fft_plan_create): channel pairs through the 8192-point engine, HALF form of mtmfft_quad_kernel
-        tw = twiddles(nfft // 2 if log2n == 14 else nfft)
-        twh = np.ascontiguousarray(twiddles(nfft)[: nfft // 4 + 1]) if log2n == 14 else None
-        lib().emu_set_twh(_p(twh, C.c_float))
-        set_blocked(blocked)
-        rc = lib().emu_mtmfft_pow2(
-            C.c_int(log2n), C.c_int(G), _p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int),
-            _p(ss, C.c_longlong), _p(sl, C.c_longlong), _p(sh, C.c_longlong), C.c_int(nseg),
-            C.c_int(nsig), C.c_int(nchan), C.c_int(K), _p(tp, C.c_float), _p(tw, C.c_float),
-            C.c_float(scale), C.c_int(detrend), C.c_int(int(demean_taper)), _p(fpos, C.c_int),
-            C.c_int(nfsel), C.c_int(kind), C.c_int(int(keeptapers)), out.ctypes.data_as(C.c_void_p))
-        set_blocked(False)
-        lib().emu_set_twh(None)
-        assert rc == 0, f"no emulated kernel for log2n={log2n} G={G}"
-        return out
-    if not force_generic and not force_long and not no_mixed:
-        # 5-smooth lengths: the packed mixed-radix engine with the schedule of spyhip_fft_plan_create
-        info = np.zeros(7, dtype=np.int32)
-        rc = lib().emu_mtmfft_mixed(
-            C.c_int(nfft), C.c_int(int(mixed_nostage)), _p(info, C.c_int), _p(data, C.c_float), C.c_longlong(ld),
-            _p(ci, C.c_int), _p(ss, C.c_longlong), _p(sl, C.c_longlong), _p(sh, C.c_longlong), C.c_int(nseg),
-            C.c_int(nsig), C.c_int(nchan), C.c_int(K), _p(tp, C.c_float), _p(twiddles(nfft), C.c_float),
-            C.c_float(scale), C.c_int(detrend), C.c_int(int(demean_taper)), _p(fpos, C.c_int), C.c_int(nfsel),
-            C.c_int(kind), C.c_int(int(keeptapers)), out.ctypes.data_as(C.c_void_p))
-        if rc == 0:
-            LAST_MIXED.update(dict(zip(("th", "G", "npass", "stage", "threads", "radix0", "radix_last"),
-                                       (int(v) for v in info))), nfft=nfft)
-            return out
-    if force_long or (not pow2 and nfft > 4096 and not force_generic):
-        # Bluestein with four-step length-M transforms through (emulated) HBM - mirror of spyhip_fft_plan_create
-        m = 12
-        while (1 << m) < 2 * nfft - 1:
-            m += 1
-        M = 1 << m
-        l1, l2 = (m + 1) // 2, m // 2
-        M1, M2 = 1 << l1, 1 << l2
-        k = np.arange(nfft, dtype=np.int64)
-        ang = np.pi * ((k * k) % (2 * nfft)) / nfft
-        chirp = np.stack([np.cos(ang), -np.sin(ang)], axis=1).astype(np.float32).copy()
-        bq = np.zeros(M, dtype=np.complex128)
-        bq[:nfft] = np.exp(1j * ang)
-        bq[M - nfft + 1:] = bq[1:nfft][::-1]
-        bh = (np.fft.fft(bq) / M).reshape(M2, M1).T                 # [k1][k2] with k = k1 + M1*k2
-        bhat = np.stack([bh.real, bh.imag], axis=-1).astype(np.float32).copy()
-        tp64 = tp.astype(np.float64)
-        mid = 0.5 * (nsig - 1)
-        wsum = np.stack([tp64.sum(axis=1), (tp64 * (np.arange(nsig) - mid)).sum(axis=1)], axis=1).copy()
-        rc = lib().emu_mtmfft_long(
-            C.c_int(l1), C.c_int(l2), C.c_int(nfft), _p(chirp, C.c_float), _p(bhat, C.c_float),
-            _p(twiddles(M1), C.c_float), _p(twiddles(M2), C.c_float), _p(twiddles(M), C.c_float),
-            wsum.ctypes.data_as(C.POINTER(C.c_double)), _p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int),
-            _p(ss, C.c_longlong), _p(sl, C.c_longlong), _p(sh, C.c_longlong), C.c_int(nseg), C.c_int(nsig),
-            C.c_int(nchan), C.c_int(K), _p(tp, C.c_float), C.c_float(scale), C.c_int(detrend),
-            C.c_int(int(demean_taper)), _p(fpos, C.c_int), C.c_int(nfsel), C.c_int(kind), C.c_int(int(keeptapers)),
-            out.ctypes.data_as(C.c_void_p))
-        assert rc == 0
-        return out
-    if 2 * nfft - 1 <= 8192 and nfft >= 2 and not force_generic:
-        # Bluestein on the packed power-of-two engine (mirror of spyhip_fft_plan_create)
-        M = 256
-        while M < 2 * nfft - 1:
-            M *= 2
-        k = np.arange(nfft, dtype=np.int64)
-        ang = np.pi * ((k * k) % (2 * nfft)) / nfft
-        chirp = np.stack([np.cos(ang), -np.sin(ang)], axis=1).astype(np.float32).copy()
-        bq = np.zeros(M, dtype=np.complex128)
-        bq[:nfft] = np.exp(1j * ang)
-        bq[M - nfft + 1:] = bq[1:nfft][::-1]
-        bh = np.fft.fft(bq) / M
-        bhat = np.stack([bh.real, bh.imag], axis=1).astype(np.float32).copy()
-        log2m = int(np.log2(M))
-        Gb = {8: 16, 9: 8, 10: 4, 11: 2, 12: 1, 13: 1}[log2m]
-        tw = twiddles(M)
-        rc = lib().emu_mtmfft_blue(
-            C.c_int(log2m), C.c_int(Gb), C.c_int(nfft), _p(chirp, C.c_float), _p(bhat, C.c_float),
-            _p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int), _p(ss, C.c_longlong), _p(sl, C.c_longlong),
-            _p(sh, C.c_longlong), C.c_int(nseg), C.c_int(nsig), C.c_int(nchan), C.c_int(K), _p(tp, C.c_float),
-            _p(tw, C.c_float), C.c_float(scale), C.c_int(detrend), C.c_int(int(demean_taper)), _p(fpos, C.c_int),
-            C.c_int(nfsel), C.c_int(kind), C.c_int(int(keeptapers)), out.ctypes.data_as(C.c_void_p))
-        assert rc == 0
-        return out
-    rad, ok = factorize(nfft)
-    n, blu, chirp, bhat = nfft, 0, None, None
-    if not ok:
-        M = 16
-        while M < 2 * nfft - 1:
-            M *= 2
-        k = np.arange(nfft, dtype=np.int64)
-        ang = np.pi * ((k * k) % (2 * nfft)) / nfft
-        chirp = np.stack([np.cos(ang), -np.sin(ang)], axis=1).astype(np.float32).copy()
-        b = np.zeros(M, dtype=np.complex128)
-        b[:nfft] = np.exp(1j * ang)
-        b[M - nfft + 1:] = b[1:nfft][::-1]
-        bh = np.fft.fft(b) / M
-        bhat = np.stack([bh.real, bh.imag], axis=1).astype(np.float32).copy()
-        n, blu = M, 1
-        rad, _ = factorize(M)
-    tw = twiddles(n)
-    radix = np.asarray(rad, dtype=np.int32)
-    stage_x = 1 if (2 * n + nsig) * 8 <= 160 * 1024 else 0
-    lib().emu_mtmfft_generic(
-        C.c_int(n), C.c_int(len(rad)), _p(radix, C.c_int), C.c_int(nfft), C.c_int(blu), _p(chirp, C.c_float),
-        _p(bhat, C.c_float), C.c_int(stage_x), _p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int),
-        _p(ss, C.c_longlong), _p(sl, C.c_longlong), _p(sh, C.c_longlong), C.c_int(nseg), C.c_int(nsig),
-        C.c_int(nchan), C.c_int(K), _p(tp, C.c_float), _p(tw, C.c_float), C.c_float(scale), C.c_int(detrend),
-        C.c_int(int(demean_taper)), _p(fpos, C.c_int), C.c_int(nfsel), C.c_int(kind), C.c_int(int(keeptapers)),
-        out.ctypes.data_as(C.c_void_p))
+    name = C.create_string_buffer(256)
+    info = np.zeros(8, dtype=np.int32)
+    rc = lib().emu_fft_exec(
+        C.c_int(nsig), C.c_int(nfft), C.c_int(nchan), C.c_int(K), _p(tp, C.c_double), C.c_double(scale), C.c_int(detrend),
+        C.c_int(int(demean_taper)), _p(fi, C.c_int), C.c_int(nfsel), C.c_int(kind), C.c_int(int(keeptapers)),
+        C.c_int(int(precision64)), C.c_int(ref_mean), C.c_int(int(blocked)), C.c_int(FORCE[force]), C.c_int(int(variant)),
+        C.c_int(int(nostage)), _p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int), _p(ss, C.c_longlong),
+        _p(sl, C.c_longlong), _p(sh, C.c_longlong), C.c_int(nseg), out.ctypes.data_as(C.c_void_p), name, C.c_int(256),
+        _p(info, C.c_int))
+    LAST_KERNEL = name.value.decode()
+    if rc == NO_INSTANCE:
+        raise NotImplementedError(f"the emulator holds no instance of {LAST_KERNEL!r} (nfft={nfft}, force={force}, {variant})")
+    if rc != 0:
+        raise RuntimeError(f"emu_fft_exec(nfft={nfft}, force={force}, {variant}) -> {rc}")
+    if LAST_KERNEL.startswith("mtmfft_mixed_kernel"):
+        LAST_MIXED.update(dict(zip(("G", "th", "npass", "stage", "threads", "radix0", "radix_last"),
+                                   (int(v) for v in info[1:]))), nfft=nfft)
+    return out, int(info[1])
+
+
+def fft_exec(data, seg_start, seg_lo, seg_hi, nsig, nfft, tapers, scale, detrend=-1, demean_taper=False,
+             freq_idx=None, output="pow", keeptapers=True, chan_idx=None, G=None, force_generic=False, blocked=False,
+             force_long=False, reference_mean=False, no_mixed=False, mixed_nostage=False, dec=None, mixed=False):
+    """Emulated spyhip_fft_exec.  data: (rows, ld) float32; tapers: (K, nsig) float64.  Without a forcing keyword the
+    kernel family is the one spyfft::fft_route gives the shape; LAST_KERNEL names it.
+    blocked: channel-blocked hand-over layout (nseg*K, ceil(nchan/4), nfsel, 4) (fourier, keeptapers).
+    reference_mean: constant detrending with the means of seq_mean_kernel (spyhip_fft_plan_set_reference_mean).
+    Forcing keywords (the filler of that family in mtmfft_route.h, whatever the route says): force_generic (the library's
+    SPYHIP_FORCE_GENERIC), force_long, no_mixed (Bluestein on the packed engine), mixed, dec (id of a compile-time
+    schedule of emu_kernels.cpp: run_dec_id; < 0: the HALF form).  mixed_nostage: the re-read path of the mixed engine.
+    G: the quads per workgroup the caller expects of the route; another value is an error."""
+    forced = [k for k, on in (("dec", dec is not None), ("generic", force_generic), ("long", force_long), ("blue", no_mixed),
+                              ("mixed", mixed)) if on]
+    assert len(forced) <= 1, forced
+    out, g = _exec(data, seg_start, seg_lo, seg_hi, nsig, nfft, tapers, scale, detrend, demean_taper, freq_idx, output,
+                   keeptapers, chan_idx, ref_mean=int(bool(reference_mean)), blocked=blocked,
+                   force=forced[0] if forced else "route", variant=0 if dec is None else dec, nostage=mixed_nostage)
+    if G is not None and G != g:
+        raise ValueError(f"G={G}: the route launches {LAST_KERNEL!r} with {g} quads per workgroup")
+    return out
+
+
+def fft_exec_f64(data, seg_start, seg_lo, seg_hi, nsig, nfft, tapers, scale, detrend=-1, demean_taper=False,
+                 freq_idx=None, output="pow", keeptapers=True, chan_idx=None, reference_mean=False, seg_f64=False,
+                 dec=None, bluestein=None, emu_id=None):
+    """Emulated spyhip_fft_exec of a plan with spyhip_fft_plan_set_precision(plan, 1); the family is the one
+    spyfft::fft_route64 gives the length unless forced: dec=True - the compile-time schedule of mtmfft_dec64_kernel for
+    this nfft, dec="half" - its HALF form (single channels through the schedule of nfft / 2; `emu_id` picks a variant that
+    shares its nfft with another, 2002), bluestein=False - the any-length kernel without the chirp-z form."""
+    force, variant = "route", 0
+    if dec == "half":
+        force, variant = "half64", -(emu_id or nfft)
+    elif dec:
+        force, variant = "dec64", nfft
+    elif bluestein is False:
+        force = "plain64"
+    out, _ = _exec(data, seg_start, seg_lo, seg_hi, nsig, nfft, tapers, scale, detrend, demean_taper, freq_idx, output,
+                   keeptapers, chan_idx, precision64=True, ref_mean=2 if seg_f64 else int(bool(reference_mean)),
+                   force=force, variant=variant)
+    if bluestein:
+        assert "Bluestein" in LAST_KERNEL, LAST_KERNEL
     return out
 
 
 def fft_exec_declong(data, seg_start, seg_lo, seg_hi, nsig, P, M, tapers, scale, detrend=-1, demean_taper=False, freq_idx=None,
                      output="pow", keeptapers=True, chan_idx=None, reference_mean=False):
-    """Emulated spyhip_fft_exec of a K1L2 plan (mtmfft_declong.h): nfft = P M, tables as spyhip_fft_plan_create builds them."""
-    data = np.ascontiguousarray(data, dtype=np.float32)
-    nfft = P * M
-    ld = data.shape[1]
-    nchan = ld if chan_idx is None else len(chan_idx)
-    ci = None if chan_idx is None else np.ascontiguousarray(chan_idx, dtype=np.int32)
-    ss = np.ascontiguousarray(seg_start, dtype=np.int64)
-    sl = np.ascontiguousarray(seg_lo, dtype=np.int64)
-    sh = np.ascontiguousarray(seg_hi, dtype=np.int64)
-    nseg, K = len(ss), tapers.shape[0]
-    tp = np.ascontiguousarray(tapers, dtype=np.float32)
-    nf = nfft // 2 + 1
-    if freq_idx is None:
-        fpos, nfsel = None, nf
-    else:
-        fi = np.asarray(freq_idx, dtype=np.int64)
-        nfsel = len(fi)
-        fpos = np.full(nf, -1, dtype=np.int32)
-        fpos[fi] = np.arange(nfsel, dtype=np.int32)
-    kind = OUT_KINDS[output]
-    out = np.full((nseg, K if keeptapers else 1, nfsel, nchan), np.nan, dtype=np.complex64 if kind == 2 else np.float32)
-    mid = 0.5 * (nsig - 1)
-    t64 = np.asarray(tapers, dtype=np.float64)
-    wsum = np.ascontiguousarray(np.stack([t64.sum(axis=1), (t64 * (np.arange(nsig) - mid)).sum(axis=1)], axis=1))
-    means = None
-    if reference_mean and detrend == 0:
-        means = seq_mean(data, ss, sl, sh, nsig, chan_idx)
-    lib().emu_set_means(_p(means, C.c_float) if means is not None else None)
-    tws, twn, twp = twiddles(M), twiddles(nfft), twiddles(P)
-    rc = lib().emu_mtmfft_declong(
-        C.c_int(P), C.c_int(M), _p(tws, C.c_float), _p(twn, C.c_float), _p(twp, C.c_float), _p(wsum, C.c_double),
-        _p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int), _p(ss, C.c_longlong), _p(sl, C.c_longlong),
-        _p(sh, C.c_longlong), C.c_int(nseg), C.c_int(nsig), C.c_int(nchan), C.c_int(K), _p(tp, C.c_float),
-        C.c_float(scale), C.c_int(detrend), C.c_int(int(demean_taper)), _p(fpos, C.c_int), C.c_int(nfsel), C.c_int(kind),
-        C.c_int(int(keeptapers)), out.ctypes.data_as(C.c_void_p))
-    lib().emu_set_means(None)
-    if rc != 0:
-        raise RuntimeError(f"emu_mtmfft_declong({P}, {M}) -> {rc}")
+    """Emulated spyhip_fft_exec of a K1L2 plan (mtmfft_declong.h), forced: nfft = P M, split as the route splits it."""
+    out, _ = _exec(data, seg_start, seg_lo, seg_hi, nsig, P * M, tapers, scale, detrend, demean_taper, freq_idx, output,
+                   keeptapers, chan_idx, ref_mean=int(bool(reference_mean)), force="declong")
+    assert LAST_KERNEL.startswith(f"declong<{P} x {M},"), LAST_KERNEL
     return out
+
+
+def seq_mean(data, seg_start, seg_lo, seg_hi, nsig, chan_idx=None):
+    """Emulated seq_mean_kernel: (nseg, nchan) float32 means in the reference's summation order."""
+    data, ld, nchan, ci, ss, sl, sh = _segments(data, seg_start, seg_lo, seg_hi, chan_idx)
+    means = np.full((len(ss), nchan), np.nan, dtype=np.float32)
+    lib().emu_seq_mean(_p(data, C.c_float), C.c_longlong(ld), _p(ci, C.c_int), _p(ss, C.c_longlong),
+                       _p(sl, C.c_longlong), _p(sh, C.c_longlong), C.c_int(len(ss)), C.c_int(nsig), C.c_int(nchan),
+                       _p(means, C.c_float))
+    return means
 
 
 def set_blocked(on):

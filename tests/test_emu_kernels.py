@@ -12,8 +12,22 @@ from parity import assert_parity, excess
 from cwt64_ref import assert_cwt64, cwt64_ref as _cwt64_ref
 
 
+def _forced_kernel(nfft, generic=False, long=False, no_mixed=False, mixed=False, dec=None):
+    """The kernel-name prefix of the family a forcing keyword asks for (None: nothing is forced)."""
+    if dec is not None:
+        return f"mtmfft_dec_kernel<HALF of N = {nfft}," if dec < 0 else f"mtmfft_dec_kernel<N = {nfft},"
+    return ("mtmfft_generic_kernel<" if generic else "mtmfft_long<" if long else "mtmfft_blue_kernel<" if no_mixed
+            else "mtmfft_mixed_kernel<" if mixed else None)
+
+
 def _fft_case(nsig, nfft, nchan, K, output, keeptapers, detrend, demean_taper=False, G=None, generic=False,
-              freq_idx=None, chan_idx=None, nseg=2, seed=1, long=False, no_mixed=False, nostage=False, dec=None):
+              freq_idx=None, chan_idx=None, nseg=2, seed=1, long=False, no_mixed=False, nostage=False, dec=None, mixed=False,
+              kernel=None):
+    """`kernel`: the prefix of the kernel name the library's route gives this shape - every un-forced case states it; a
+    forced case runs, and is checked for, the family of its forcing keyword (`mixed`: the mixed-radix engine on a length
+    the route gives a compile-time schedule)."""
+    forced = _forced_kernel(nfft, generic, long, no_mixed, mixed, dec)
+    assert (forced is None) != (kernel is None), "state the expected kernel of an un-forced case (and only of those)"
     rng = np.random.default_rng(seed)
     data = rng.normal(size=(nsig * nseg + 9, nchan)).astype("f4")
     ss = np.array([4 + i * nsig for i in range(nseg)])
@@ -21,7 +35,8 @@ def _fft_case(nsig, nfft, nchan, K, output, keeptapers, detrend, demean_taper=Fa
     tapers = O.taper_table(taper, nsig, nfft, topt)
     out = E.fft_exec(data, ss, ss, ss + nsig, nsig, nfft, tapers, O.spec_scale(nsig, nfft), detrend, demean_taper,
                      freq_idx, output, keeptapers, chan_idx=chan_idx, G=G, force_generic=generic, force_long=long,
-                     no_mixed=no_mixed, mixed_nostage=nostage, dec=dec)
+                     no_mixed=no_mixed, mixed_nostage=nostage, dec=dec, mixed=mixed)
+    assert E.LAST_KERNEL.startswith(forced or kernel), (E.LAST_KERNEL, forced or kernel)
     freqs = np.fft.rfftfreq(nfft, 1e-3)
     foi = freqs if freq_idx is None else freqs[freq_idx]
     for b in range(nseg):
@@ -38,16 +53,18 @@ def _fft_case(nsig, nfft, nchan, K, output, keeptapers, detrend, demean_taper=Fa
 def test_pow2_kernel_every_length(log2n, G):
     n = 1 << log2n
     nchan = 4 * G + 1 if n <= 2048 else (5 if n == 4096 else 3)   # ragged channel count: padded quads / pairs
-    _fft_case(n, n, nchan, 2, "pow", False, 0, G=G, nseg=1)
+    # (2^14: channel pairs through the 8192-point engine)
+    _fft_case(n, n, nchan, 2, "pow", False, 0, G=G, nseg=1,
+              kernel="mtmfft_quad_kernel<13, 1, 0, true, HALF of N = 16384>" if log2n == 14 else f"mtmfft_quad_kernel<{log2n}, {G}, 0, true>")
 
 
 def test_pow2_kernel_full_quads_fast_epilogue():
     # channel counts that are multiples of 4 with every bin kept take the straight-line store path
-    _fft_case(1024, 1024, 8, 2, "pow", True, 0)
-    _fft_case(512, 512, 4, 2, "fourier", True, 0)
-    _fft_case(256, 256, 8, 3, "pow", False, 1)
-    _fft_case(512, 512, 8, 2, "abs", True, -1)
-    _fft_case(300, 512, 6, 2, "fourier", True, 0)       # even, not a multiple of 4
+    _fft_case(1024, 1024, 8, 2, "pow", True, 0, kernel="mtmfft_quad_kernel<10, 4, 0, false>")
+    _fft_case(512, 512, 4, 2, "fourier", True, 0, kernel="mtmfft_quad_kernel<9, 8, 2, false>")
+    _fft_case(256, 256, 8, 3, "pow", False, 1, kernel="mtmfft_quad_kernel<8, 16, 0, true>")
+    _fft_case(512, 512, 8, 2, "abs", True, -1, kernel="mtmfft_quad_kernel<9, 8, 1, false>")
+    _fft_case(300, 512, 6, 2, "fourier", True, 0, kernel="mtmfft_quad_kernel<9, 8, 2, false>")       # even, not a multiple of 4
 
 
 @pytest.mark.parametrize("C,N,B,K", [(5, 256, 2, 1), (8, 512, 2, 2), (37, 256, 2, 1)])
@@ -60,6 +77,7 @@ def test_blocked_handover_layout(C, N, B, K):
     F = N // 2 + 1
     std = E.fft_exec(data, ss, ss, ss + N, N, N, tapers, np.sqrt(2) / N, 0, False, None, "fourier", True)
     blk = E.fft_exec(data, ss, ss, ss + N, N, N, tapers, np.sqrt(2) / N, 0, False, None, "fourier", True, blocked=True)
+    assert E.LAST_KERNEL == {256: "mtmfft_quad_kernel<8, 16, 2, false>", 512: "mtmfft_quad_kernel<9, 8, 2, false>"}[N]
     nq = (C + 3) // 4
     got = blk.transpose(0, 2, 1, 3).reshape(B * K, F, 4 * nq)      # back to (rows, F, padded channels)
     np.testing.assert_array_equal(got[:, :, :C], std.reshape(B * K, F, C))
@@ -74,10 +92,11 @@ def test_blocked_handover_layout(C, N, B, K):
 
 
 def test_pow2_kernel_modes():
-    _fft_case(1000, 1024, 5, 3, "fourier", True, 1, demean_taper=True)
-    _fft_case(1024, 1024, 5, 3, "fourier", False, 0)
-    _fft_case(700, 1024, 4, 1, "abs", True, -1)
-    _fft_case(512, 512, 6, 2, "real", False, 0, freq_idx=np.array([5, 0, 256, 100]), chan_idx=[5, 5, 0, 3, 1])
+    _fft_case(1000, 1024, 5, 3, "fourier", True, 1, demean_taper=True, kernel="mtmfft_quad_kernel<10, 4, 2, false>")
+    _fft_case(1024, 1024, 5, 3, "fourier", False, 0, kernel="mtmfft_quad_kernel<10, 4, 2, true>")
+    _fft_case(700, 1024, 4, 1, "abs", True, -1, kernel="mtmfft_quad_kernel<10, 4, 1, false>")
+    _fft_case(512, 512, 6, 2, "real", False, 0, freq_idx=np.array([5, 0, 256, 100]), chan_idx=[5, 5, 0, 3, 1],
+              kernel="mtmfft_quad_kernel<9, 8, 1, true>")
 
 
 @pytest.mark.parametrize("nsig,nfft", [(2000, 2000), (500, 1000), (360, 360), (77, 154), (101, 202), (64, 64)])
@@ -97,14 +116,33 @@ def test_long_transform_path():
     _fft_case(2500, 2500, 3, 1, "abs", True, -1, long=True, nseg=1, freq_idx=np.array([7, 0, 1250, 333]))
 
 
+@pytest.mark.parametrize("nfft,kernel", [
+    (4116, "mtmfft_generic_kernel<"),       # 2^2 x 3 x 7^3: 13-smooth, above 4096, refused by the mixed engine - stays in LDS
+    (4097, "mtmfft_long<128 x 128"),        # 17 x 241 above 2048: no in-LDS Bluestein, four-step transforms of 16384 points
+])
+def test_route_of_awkward_lengths_above_4096(nfft, kernel):
+    """Shapes on which a restatement of the route once disagreed with spyfft::fft_route (it sent every such length through
+    HBM): the emulator launches what the library launches."""
+    _fft_case(nfft, nfft, 2, 1, "fourier", True, 0, nseg=1, kernel=kernel)
+
+
+def test_forcing_keywords_are_checked():
+    with pytest.raises(ValueError):         # 1024 runs four quads per workgroup
+        _fft_case(1024, 1024, 4, 1, "pow", True, 0, G=2, nseg=1, kernel="mtmfft_quad_kernel<10, 4,")
+    with pytest.raises(NotImplementedError):    # the route's choice, of which the emulator holds no instance: no substitute runs
+        _fft_case(800, 800, 4, 1, "pow", True, 0, nseg=1, kernel="mtmfft_dec_kernel<N = 800,")
+
+
 def test_bluestein_kernel_modes():
     _fft_case(500, 500, 8, 1, "pow", True, 0, no_mixed=True)       # full quads: float4 stores
     _fft_case(500, 500, 5, 3, "abs", False, 1, no_mixed=True)
     _fft_case(300, 360, 6, 2, "fourier", False, -1, no_mixed=True)
-    _fft_case(77, 77, 4, 2, "real", True, 0, freq_idx=np.array([3, 0, 38, 20]), chan_idx=[3, 3, 0, 1])
+    # (un-forced from here: 77 = 7 x 11 is not 5-smooth, and the mixed engine serves no length below 16)
+    _fft_case(77, 77, 4, 2, "real", True, 0, freq_idx=np.array([3, 0, 38, 20]), chan_idx=[3, 3, 0, 1],
+              kernel="mtmfft_blue_kernel<8, 16, 1, false>")
     for n in (3, 5, 7, 13):                                        # trials of a handful of samples
-        _fft_case(n, n, 3, 1, "fourier", True, 0, nseg=2)
-    _fft_case(3, 8, 2, 1, "pow", False, -1, nseg=1)
+        _fft_case(n, n, 3, 1, "fourier", True, 0, nseg=2, kernel="mtmfft_blue_kernel<8, 16, 2, false>")
+    _fft_case(3, 8, 2, 1, "pow", False, -1, nseg=1, kernel="mtmfft_blue_kernel<8, 16, 0, true>")
 
 
 @pytest.mark.parametrize("nsig,nfft,sched", [
@@ -116,22 +154,26 @@ def test_bluestein_kernel_modes():
     (64, 64, (8, 8, 8)), (16, 16, (2, 8, 2)), (25, 30, (4, 3, 10)), (1215, 1215, (135, 5, 3)),
 ])
 def test_mixed_radix_kernel_lengths(nsig, nfft, sched):
-    """K1m, the packed engine for 5-smooth lengths, with the schedule mix_schedule (the code plan_create runs) picks."""
-    _fft_case(nsig, nfft, 5, 2, "pow", False, 0, nseg=2)
+    """K1m, the packed engine for 5-smooth lengths, with the schedule mix_schedule (the code plan_create runs) picks.
+    1000, 2000, 3000 and 5000 have compile-time schedules in the library: the route gives them to mtmfft_dec_kernel, and
+    the mixed engine runs them here through its filler (`mixed`), as the library would a length without a schedule."""
+    how = dict(mixed=True) if nfft in (1000, 2000, 3000, 5000) else dict(kernel="mtmfft_mixed_kernel<")
+    _fft_case(nsig, nfft, 5, 2, "pow", False, 0, nseg=2, **how)
     assert E.LAST_MIXED["nfft"] == nfft
     assert (E.LAST_MIXED["th"], E.LAST_MIXED["radix0"], E.LAST_MIXED["radix_last"]) == sched
-    _fft_case(nsig, nfft, 2, 1, "fourier", True, 1, demean_taper=True, nseg=1)
+    _fft_case(nsig, nfft, 2, 1, "fourier", True, 1, demean_taper=True, nseg=1, **how)
 
 
 def test_mixed_radix_kernel_modes():
-    _fft_case(500, 500, 8, 1, "pow", True, 0)                      # full quads: float4 stores
-    _fft_case(500, 500, 5, 3, "abs", False, 1)
-    _fft_case(300, 360, 6, 2, "fourier", False, -1)
-    _fft_case(300, 360, 9, 2, "fourier", True, 0, demean_taper=True, nostage=True)     # the re-read path on a short length
-    _fft_case(250, 250, 17, 2, "pow", False, 1, nostage=True, nseg=3)                 # several quad groups, ragged last quad
-    _fft_case(80, 80, 4, 2, "real", True, 0, freq_idx=np.array([3, 0, 40, 20]), chan_idx=[3, 3, 0, 1])
-    _fft_case(150, 150, 4, 3, "angle", False, -1)
-    _fft_case(36, 36, 4, 1, "fourier", True, 0)                     # 3 x 3 x 4
+    _fft_case(500, 500, 8, 1, "pow", True, 0, mixed=True)          # full quads: float4 stores (500 has a compile-time schedule)
+    _fft_case(500, 500, 5, 3, "abs", False, 1, mixed=True)
+    mk = "mtmfft_mixed_kernel<"
+    _fft_case(300, 360, 6, 2, "fourier", False, -1, kernel=mk + "2, true> N=360 (5x3x3x8)")
+    _fft_case(300, 360, 9, 2, "fourier", True, 0, demean_taper=True, nostage=True, kernel=mk)     # the re-read path on a short length
+    _fft_case(250, 250, 17, 2, "pow", False, 1, nostage=True, nseg=3, kernel=mk)      # several quad groups, ragged last quad
+    _fft_case(80, 80, 4, 2, "real", True, 0, freq_idx=np.array([3, 0, 40, 20]), chan_idx=[3, 3, 0, 1], kernel=mk)
+    _fft_case(150, 150, 4, 3, "angle", False, -1, kernel=mk)
+    _fft_case(36, 36, 4, 1, "fourier", True, 0, kernel=mk + "2, false> N=36 (3x3x4)")               # 3 x 3 x 4
     assert E.LAST_MIXED["nfft"] == 36 and E.LAST_MIXED["radix_last"] == 4
 
 
@@ -148,6 +190,7 @@ def test_zero_extended_segments():
     hi = np.array([1000, 1000, 1000, 420])
     tapers = O.taper_table("hann", nsig, nfft)
     out = E.fft_exec(data, starts, lo, hi, nsig, nfft, tapers, np.sqrt(2) / nsig, 0, False, None, "fourier", True)
+    assert E.LAST_KERNEL == "mtmfft_quad_kernel<8, 16, 2, false>"
     for b in range(4):
         seg = np.zeros((nsig, 4), "f4")
         for n in range(nsig):
@@ -166,6 +209,7 @@ def test_fp32_fft_error_level():
     data = rng.normal(size=(n, 4)).astype("f4")
     z = np.array([0])
     out = E.fft_exec(data, z, z, z + n, n, n, np.ones((1, n)), 1.0, -1, False, None, "fourier", True)[0, 0]
+    assert E.LAST_KERNEL == "mtmfft_quad_kernel<12, 2, 2, false>"       # complex spectra of every taper: two quads per workgroup
     ref = np.fft.rfft(data.astype("f8"), axis=0)
     rms = np.sqrt((np.abs(ref) ** 2).mean())
     assert np.abs(out - ref).max() / rms < 1e-6
@@ -890,7 +934,8 @@ def test_reference_order_mean_is_numpy_bit_for_bit():
     assert seq / np.float32(4096) != np.mean(np.ascontiguousarray(x[:4096, 3:4]), axis=0)[0]    # (the orders do differ)
 
 
-@pytest.mark.parametrize("nsig,nfft,kw", [(4096, 4096, {}), (1000, 1024, {}), (2000, 2000, {}),
+# (2000 forced: the route gives it its compile-time schedule; this case has always run the mixed-radix engine)
+@pytest.mark.parametrize("nsig,nfft,kw", [(4096, 4096, {}), (1000, 1024, {}), (2000, 2000, {"mixed": True}),
                                           (600, 600, {"force_generic": True}), (5003, 5003, {"force_long": True}),
                                           (16384, 16384, {})])
 def test_offset_channels_match_the_reference_next_to_dc(nsig, nfft, kw):
@@ -908,6 +953,9 @@ def test_offset_channels_match_the_reference_next_to_dc(nsig, nfft, kw):
     ref, _ = O.mtmfft(O.detrend(x, 0), 1000.0, nfft, "dpss", topt)
     got = E.fft_exec(x, [0], [0], [nsig], nsig, nfft, tap, sc, detrend=0, output="fourier", keeptapers=True,
                      reference_mean=True, **kw)[0]
+    kernel = {4096: "mtmfft_quad_kernel<12, 2, 2, false>", 1024: "mtmfft_quad_kernel<10, 4, 2, false>", 2000: "mtmfft_mixed_kernel<",
+              600: "mtmfft_generic_kernel<", 5003: "mtmfft_long<128 x 128,", 16384: "mtmfft_quad_kernel<13, 1, 2, false, HALF of N = 16384>"}[nfft]
+    assert E.LAST_KERNEL.startswith(kernel), E.LAST_KERNEL
     for c in range(C):                       # per channel: the criterion relative to THAT channel's largest bin
         assert_parity(got[:, :, c], ref[:, :, c], what=f"channel {c} with reference-order mean")
     plain = E.fft_exec(x, [0], [0], [nsig], nsig, nfft, tap, sc, detrend=0, output="fourier", keeptapers=True, **kw)[0]
@@ -1050,9 +1098,13 @@ def test_csd_3m_more_than_512_channels():
 
 # K1r second generation: reference-precision transforms (mtmfft_dec64_kernel.h, mtmfft_f64_kernel.h incl. Bluestein)
 def _f64_case(nsig, nfft, nchan, K, output, keeptapers, detrend, demean_taper=False, freq_idx=None, chan_idx=None, nseg=1,
-              seed=3, dec=True, bluestein=False, pure_frac=0.99, emu_id=None):
+              seed=3, dec=None, bluestein=None, pure_frac=0.99, emu_id=None, kernel=None):
     """Data with 60 dB of dynamic range (a 40 Hz line 1000 x the noise, an offset): the criterion everywhere, and for
-    complex output PURE rtol 1e-5 bin by bin on >= 99 % of the bins - which only a float64 transform delivers."""
+    complex output PURE rtol 1e-5 bin by bin on >= 99 % of the bins - which only a float64 transform delivers.
+    The family is the one spyfft::fft_route64 gives nfft, and `kernel` the prefix of its name - by default the compile-time
+    schedule of nfft; dec=True / dec="half" / bluestein=False force a family (emu_driver.fft_exec_f64)."""
+    if kernel is None:
+        kernel = f"mtmfft_dec64_kernel<HALF of N = {nfft}," if dec == "half" else f"mtmfft_dec64_kernel<N = {nfft},"
     rng = np.random.default_rng(seed)
     t = np.arange(nsig * nseg + 9) / 1000.0
     data = (rng.normal(size=(nsig * nseg + 9, nchan)) + 1000.0 * np.sin(2 * np.pi * 40.0 * t)[:, None] + 50.0).astype("f4")
@@ -1062,6 +1114,7 @@ def _f64_case(nsig, nfft, nchan, K, output, keeptapers, detrend, demean_taper=Fa
     out = E.fft_exec_f64(data, ss, ss, ss + nsig, nsig, nfft, tapers, O.spec_scale(nsig, nfft), detrend, demean_taper,
                          freq_idx, output, keeptapers, chan_idx=chan_idx, reference_mean=True, dec=dec, bluestein=bluestein,
                          emu_id=emu_id)
+    assert E.LAST_KERNEL.startswith(kernel), (E.LAST_KERNEL, kernel)
     freqs = np.fft.rfftfreq(nfft, 1e-3)
     foi = freqs if freq_idx is None else freqs[freq_idx]
     for b in range(nseg):
@@ -1087,7 +1140,8 @@ def test_dec64_kernel_vs_oracle(nfft, nchan, K):
 @pytest.mark.parametrize("nfft", [8192, 16384, 4000, 5000, 10000])
 def test_dec64_kernel_long_schedules(nfft):
     # 8192: four passes; 16384: 1024 threads, split exchange, samples re-read per taper; 10000: split exchange, V = 20
-    _f64_case(nfft, nfft, 2, 1, "fourier", True, 0)
+    # (16384 forced: the route gives it the HALF form, single channels through the schedule of 8192)
+    _f64_case(nfft, nfft, 2, 1, "fourier", True, 0, dec=True if nfft == 16384 else None)
 
 
 @pytest.mark.parametrize("nfft,nchan,K", [(100, 35, 2), (300, 17, 2), (400, 9, 2), (2400, 3, 1), (3200, 2, 1), (600, 9, 2), (768, 5, 2), (1500, 5, 2), (3000, 3, 2), (3072, 2, 1), (6000, 2, 1),
@@ -1121,12 +1175,12 @@ def test_dec64_kernel_options():
     (1200, 1200, 5, 2, "fourier", True, 0, True, None),      # 3 x 200: radix-3 decimation in front
     (1100, 1200, 3, 2, "pow", False, 1, False, None),
     (1024, 1024, 3, 2, "pow", True, 0, False, None),         # powers from the table (no hoisted base twiddles)
-    (12000, 12000, 1, 1, "fourier", True, 0, False, None),   # the product's schedule for nfft = 12000
+    (12000, 12000, 1, 1, "fourier", True, 0, False, None),   # the product's schedule for nfft = 12000: un-forced
 ])
 def test_dec64_kernel_half_form(nsig, nfft, nchan, K, output, keeptapers, detrend, demean, emu_id):
     """CfgD64::HALF: one channel = one complex128 transform of (even, odd) samples through the schedule of nfft / 2."""
     _f64_case(nsig, nfft, nchan, K, output, keeptapers, detrend, demean_taper=demean, nseg=2 if nfft <= 2000 else 1,
-              dec="half", emu_id=emu_id)
+              dec=None if nfft == 12000 else "half", emu_id=emu_id, kernel=f"mtmfft_dec64_kernel<HALF of N = {nfft},")
 
 
 def test_dec64_kernel_half_form_selection():
@@ -1139,6 +1193,10 @@ def test_dec64_kernel_half_form_selection():
                                                      (3001, 1, 1, True), (268, 2, 1, False)])
 def test_f64_any_kernel_and_bluestein_vs_oracle(nfft, nchan, K, bluestein):
     # 1009 and 3001 are primes, 134 = 2 x 67, 268 = 4 x 67 through the O(R^2) pass AND through the chirp-z form
-    _f64_case(nfft, nfft, nchan, K, "fourier", True, 0, dec=False, bluestein=bluestein)
+    # (the route takes the chirp-z form beyond a prime factor of 61: 268 without it is forced)
+    name = f"mtmfft_f64_any_kernel<2, false> N={nfft}"
+    _f64_case(nfft, nfft, nchan, K, "fourier", True, 0, bluestein=False if nfft == 268 else bluestein or None,
+              kernel=name + " (Bluestein, M = " if bluestein else name)
+    assert ("Bluestein" in E.LAST_KERNEL) == bluestein
     if nfft == 268:
-        _f64_case(nfft, nfft, nchan, K, "fourier", True, 0, dec=False, bluestein=True)
+        _f64_case(nfft, nfft, nchan, K, "fourier", True, 0, bluestein=True, kernel=name + " (Bluestein, M = 1024)")
