@@ -46,11 +46,7 @@ int launch_lags(spyhip_ctx* ctx, const spyfft::CcovArgs& a) {
 }
 int normalize(spyhip_ctx* ctx, float* out, const float2* acc, int nlag, int nchan, int mode, float dc) {
     const size_t need = (size_t)nchan * sizeof(float);
-    if (need > ctx->scratch_bytes) {
-        if (ctx->scratch) { (void)hipFree(ctx->scratch); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
-        SPY_HIP_CHECK(hipMalloc(&ctx->scratch, need));
-        ctx->scratch_bytes = need;
-    }
+    if (spy::reserve_scratch(ctx, need)) return -2;
     float* d = reinterpret_cast<float*>(ctx->scratch);
     hipLaunchKernelGGL(spyfft::ccov_diag_kernel, dim3((nchan + 255) / 256), dim3(256), 0, ctx->stream,
                        out, acc, nchan, mode, dc, d);

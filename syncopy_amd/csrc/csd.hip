@@ -57,11 +57,7 @@ int launch_tail(spyhip_ctx* ctx, CsdArgs a, const CsdStep& s) {
     if (nsplit < 2) return launch_accum<1, 1>(ctx, a, s);
     const int f0 = (int)(s.item0 / a.ntiles), nf = a.F - f0;
     const size_t need = (size_t)(nsplit - 1) * nf * a.C * a.C * sizeof(float2);
-    if (need > ctx->scratch_bytes) {
-        if (ctx->scratch) { (void)hipFree(ctx->scratch); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
-        SPY_HIP_CHECK(hipMalloc(&ctx->scratch, need));
-        ctx->scratch_bytes = need;
-    }
+    if (spy::reserve_scratch(ctx, need)) return -2;
     a.rows_per_split = s.split.rows_per_split;
     a.part = reinterpret_cast<float2*>(ctx->scratch);
     a.part_f0 = f0;

@@ -154,11 +154,7 @@ int plus(spyhip_ctx* ctx, int L, const spywil::PlusPlan& pl, const cd* g, int F,
         case spywil::Plus::LDS:
             return launch(ctx, spywil::plus_kernel, dim3((unsigned)r.grid), r.threads, r.lds, g, F, nent, pl, tw, gp, g0);
         case spywil::Plus::LONG:
-            if (r.scratch_bytes > ctx->scratch_bytes) {
-                if (ctx->scratch) { SPY_HIP_CHECK(hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->scratch); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
-                SPY_HIP_CHECK(hipMalloc(&ctx->scratch, r.scratch_bytes));
-                ctx->scratch_bytes = r.scratch_bytes;
-            }
+            if (spy::reserve_scratch(ctx, r.scratch_bytes)) return -2;
             for (long long e0 = 0; e0 < nent; e0 += r.chunk)
                 if (launch(ctx, spywil::plus_long_kernel, dim3((unsigned)std::min(r.chunk, nent - e0)), r.threads, 0, g, F, nent, pl, tw,
                            gp, g0, reinterpret_cast<cd*>(ctx->scratch), e0))

@@ -18,20 +18,6 @@ namespace {
 
 using spyhil::Family;
 
-// the context's scratch buffer with room for `need` bytes
-int reserve_scratch(spyhip_ctx* ctx, size_t need) {
-    if (need <= ctx->scratch_bytes) return 0;
-    if (ctx->scratch) {
-        SPY_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->scratch);
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-    }
-    SPY_HIP_CHECK(hipMalloc(&ctx->scratch, need));
-    ctx->scratch_bytes = need;
-    return 0;
-}
-
 int exec_packed(spyhip_hilbert_plan* p, spyhil::HilArgs& a, bool cplx) {
     const spyhil::Route& r = p->r;
     // offsets inside one trial are 32-bit byte offsets of the wider of the two arrays
@@ -60,8 +46,9 @@ int exec_any64(spyhip_hilbert_plan* p, const spyhil::HilArgs& h, bool cplx) {
     a.tw = p->tw64.p; a.chirp = p->chirp64.p; a.bhat = p->bhat64.p;
     const long long total = (long long)h.ntrials * ((h.nchan + 1) / 2);
     long long chunk = spyhil::any64_chunk(r.M);
+    if (chunk > p->ctx->limits.any64_chunk) chunk = p->ctx->limits.any64_chunk;
     if (chunk > total) chunk = total;
-    if (reserve_scratch(p->ctx, (size_t)chunk * 2 * (size_t)r.M * sizeof(double2))) return -2;
+    if (spy::reserve_scratch(p->ctx, (size_t)chunk * 2 * (size_t)r.M * sizeof(double2))) return -2;
     a.work = reinterpret_cast<double2*>(p->ctx->scratch);
     for (long long w0 = 0; w0 < total; w0 += chunk) {       // launches on one stream: each owns the work arrays in turn
         a.wg0 = w0;

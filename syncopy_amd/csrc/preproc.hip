@@ -12,7 +12,6 @@ using spypre::SosCoef;
 // the FIR tile the library launches: 16 outputs per lane, 8 waves, 128 taps per LDS stage (65 280 bytes of LDS, two
 // workgroups per CU)
 constexpr int FIR_R = 16, FIR_NT = 8, FIR_KC = 128;
-using FirCfg = spypre::FirTile<FIR_R, FIR_NT, FIR_KC>;
 
 // shapes every kernel here can address: offsets inside one trial are 32-bit, one thread per series
 int check_batch(const char* who, int64_t ntrials, int64_t nsamp, int64_t nchan, int64_t extra_rows) {
@@ -45,6 +44,36 @@ int fill_sos(const char* who, const double* sos, const double* zi, int nsec, Sos
         if (r[3] != 1.0) { spy::set_error("%s: section %d is not normalised (a0 = %g)", who, s, r[3]); return -1; }
         k->c[s][0] = r[0]; k->c[s][1] = r[1]; k->c[s][2] = r[2]; k->c[s][3] = r[4]; k->c[s][4] = r[5];
         if (zi) { k->zi[s][0] = zi[2 * s]; k->zi[s][1] = zi[2 * s + 1]; }
+    }
+    return 0;
+}
+
+// spyhip_fir_same behind its pointer checks, on the tile FirTile<R, NT, KC>
+template <int R, int NT, int KC>
+int fir_launch(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t ntrials, int64_t nsamp, int64_t nchan,
+               const double* taps_d, int ntaps, int rectify, int32_t* nan_d) {
+    using Tile = spypre::FirTile<R, NT, KC>;
+    if (check_batch("fir_same", ntrials, nsamp, nchan, 0)) return -1;
+    // the staging of a tile looks (ntaps + tile) samples to either side of it
+    if (nsamp + (int64_t)ntaps + Tile::T + KC > (int64_t)INT_MAX / 2) { spy::set_error("fir_same: %d taps on %lld samples", ntaps, (long long)nsamp); return -1; }
+    const int64_t max_yz = ctx->limits.grid_yz;
+    const int64_t ytiles = (nsamp + Tile::T - 1) / Tile::T;
+    if (ytiles > max_yz) { spy::set_error("fir_same: %lld samples per trial (at most %lld)", (long long)nsamp, (long long)(max_yz * Tile::T)); return -1; }
+    if (ntrials == 0) return 0;
+    SPY_HIP_CHECK(hipSetDevice(ctx->device));
+    const int N = (int)nsamp, C = (int)nchan;
+    for (int64_t t0 = 0; t0 < ntrials; t0 += max_yz) {          // grid.z carries the trial
+        const unsigned nz = (unsigned)((ntrials - t0) < max_yz ? (ntrials - t0) : max_yz);
+        const dim3 g((unsigned)((nchan + 63) / 64), (unsigned)ytiles, nz), b(Tile::THREADS);
+        const float* in = in_d + t0 * nsamp * nchan;
+        float* out = out_d + t0 * nsamp * nchan;
+        if (rectify)
+            hipLaunchKernelGGL((spypre::fir_same_kernel<R, NT, KC, true>), g, b, Tile::LDS_BYTES, ctx->stream,
+                               in, out, taps_d, ntaps, N, C, nan_d + t0);
+        else
+            hipLaunchKernelGGL((spypre::fir_same_kernel<R, NT, KC, false>), g, b, Tile::LDS_BYTES, ctx->stream,
+                               in, out, taps_d, ntaps, N, C, nan_d + t0);
+        SPY_HIP_CHECK(hipGetLastError());
     }
     return 0;
 }
@@ -133,26 +162,5 @@ extern "C" int spyhip_sosfiltfilt(spyhip_ctx* ctx, const float* in_d, float* out
 extern "C" int spyhip_fir_same(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t ntrials, int64_t nsamp,
                                int64_t nchan, const double* taps_d, int ntaps, int rectify, int32_t* nan_d) {
     if (!ctx || !in_d || !out_d || !nan_d || !taps_d || ntaps < 1 || in_d == out_d) { spy::set_error("fir_same: bad argument"); return -1; }
-    if (check_batch("fir_same", ntrials, nsamp, nchan, 0)) return -1;
-    // the staging of a tile looks (ntaps + tile) samples to either side of it
-    if (nsamp + (int64_t)ntaps + FirCfg::T + FIR_KC > (int64_t)INT_MAX / 2) { spy::set_error("fir_same: %d taps on %lld samples", ntaps, (long long)nsamp); return -1; }
-    const int64_t ytiles = (nsamp + FirCfg::T - 1) / FirCfg::T;
-    if (ytiles > 65535) { spy::set_error("fir_same: %lld samples per trial (at most %d)", (long long)nsamp, 65535 * FirCfg::T); return -1; }
-    if (ntrials == 0) return 0;
-    SPY_HIP_CHECK(hipSetDevice(ctx->device));
-    const int N = (int)nsamp, C = (int)nchan;
-    for (int64_t t0 = 0; t0 < ntrials; t0 += 65535) {          // grid.z carries the trial
-        const unsigned nz = (unsigned)((ntrials - t0) < 65535 ? (ntrials - t0) : 65535);
-        const dim3 g((unsigned)((nchan + 63) / 64), (unsigned)ytiles, nz), b(FirCfg::THREADS);
-        const float* in = in_d + t0 * nsamp * nchan;
-        float* out = out_d + t0 * nsamp * nchan;
-        if (rectify)
-            hipLaunchKernelGGL((spypre::fir_same_kernel<FIR_R, FIR_NT, FIR_KC, true>), g, b, FirCfg::LDS_BYTES, ctx->stream,
-                               in, out, taps_d, ntaps, N, C, nan_d + t0);
-        else
-            hipLaunchKernelGGL((spypre::fir_same_kernel<FIR_R, FIR_NT, FIR_KC, false>), g, b, FirCfg::LDS_BYTES, ctx->stream,
-                               in, out, taps_d, ntaps, N, C, nan_d + t0);
-        SPY_HIP_CHECK(hipGetLastError());
-    }
-    return 0;
+    return fir_launch<FIR_R, FIR_NT, FIR_KC>(ctx, in_d, out_d, ntrials, nsamp, nchan, taps_d, ntaps, rectify, nan_d);
 }

@@ -7,7 +7,6 @@
 
 namespace {
 
-constexpr int64_t MAX_YZ = 65535;            // blocks along grid.y / grid.z
 constexpr int64_t MAX_TABLE = 1LL << 24;     // entries of the (channel, unit) tables
 
 bool table_ok(const char* what, int64_t nchan, int64_t nunit) {
@@ -24,10 +23,11 @@ bool trials_ok(const char* what, int64_t ntrials) {
     return true;
 }
 
-bool shape_ok(const char* what, int64_t ntrials, int64_t nbins, int64_t ncols) {
+bool shape_ok(const spyhip_ctx* ctx, const char* what, int64_t ntrials, int64_t nbins, int64_t ncols) {
     if (!trials_ok(what, ntrials)) return false;
-    if (nbins < 1 || ncols < 1 || (nbins + spypsth::BIN_TILE - 1) / spypsth::BIN_TILE > MAX_YZ ||
-        (ncols + spypsth::PROP_TILE - 1) / spypsth::PROP_TILE > MAX_YZ ||
+    const int64_t max_yz = ctx->limits.grid_yz;         // blocks along grid.y / grid.z
+    if (nbins < 1 || ncols < 1 || (nbins + spypsth::BIN_TILE - 1) / spypsth::BIN_TILE > max_yz ||
+        (ncols + spypsth::PROP_TILE - 1) / spypsth::PROP_TILE > max_yz ||
         (ntrials > 0 && nbins + 1 > (INT64_MAX >> 3) / ntrials / ncols)) {
         spy::set_error("%s: %lld trials of %lld bins x %lld columns", what, (long long)ntrials, (long long)nbins,
                        (long long)ncols);
@@ -89,7 +89,7 @@ extern "C" int spyhip_psth_count(spyhip_ctx* ctx, const int32_t* chan_d, const i
         spy::set_error("psth_count: bad argument");
         return -1;
     }
-    if (!shape_ok("psth_count", ntrials, nbins, ncols) || !table_ok("psth_count", nchan, nunit)) return -1;
+    if (!shape_ok(ctx, "psth_count", ntrials, nbins, ncols) || !table_ok("psth_count", nchan, nunit)) return -1;
     if (ntrials == 0) return 0;
     SPY_HIP_CHECK(hipSetDevice(ctx->device));
     const dim3 grid((unsigned)ntrials, (unsigned)((nbins + spypsth::BIN_TILE - 1) / spypsth::BIN_TILE),
@@ -111,8 +111,8 @@ extern "C" int spyhip_psth_proportion(spyhip_ctx* ctx, const int32_t* chan_d, co
         spy::set_error("psth_proportion: bad argument");
         return -1;
     }
-    if (!shape_ok("psth_proportion", ntrials, nbins, ncols) || !table_ok("psth_proportion", nchan, nunit)) return -1;
-    if (nk < 1 || nk > nunit || (nk + spypsth::UNIT_TILE - 1) / spypsth::UNIT_TILE > MAX_YZ) {
+    if (!shape_ok(ctx, "psth_proportion", ntrials, nbins, ncols) || !table_ok("psth_proportion", nchan, nunit)) return -1;
+    if (nk < 1 || nk > nunit || (nk + spypsth::UNIT_TILE - 1) / spypsth::UNIT_TILE > ctx->limits.grid_yz) {
         spy::set_error("psth_proportion: %lld units with a column", (long long)nk);
         return -1;
     }

@@ -1,6 +1,7 @@
 // Shared host-side plumbing of libspyhip: context, error reporting, launch checks.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <climits>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -12,6 +13,15 @@
 
 #include "spy_intrinsics.h"
 #include "spy_launch.h"      // dispatch_mode, xcd_grid, for_seg_launches
+
+// What one launch may ask of the device.  The launchers read these instead of literals; nothing in the API sets them
+// (the CPU emulator of tests/emu lowers them so that the chunk loops and grid-stride loops run at test sizes).
+struct spyhip_limits {
+    int64_t grid_yz = 65535;            // blocks along grid.y / grid.z
+    int64_t elementwise_blocks = 4096;  // workgroups of the grid-stride kernels of stats.hip
+    int64_t workgroups = 65535;         // workgroups of the median, variance and transposition launches
+    int64_t any64_chunk = INT64_MAX;    // work arrays of one float64 Hilbert launch, on top of spyhil::any64_chunk
+};
 
 struct spyhip_ctx {
     int device = 0;
@@ -33,6 +43,7 @@ struct spyhip_ctx {
     int granger_iters = 0;          // Wilson iterations of the last spyhip_granger call on this context
     int num_cu = 256;
     size_t lds_per_block = 160 * 1024;
+    spyhip_limits limits;
 };
 
 namespace spy {
@@ -79,6 +90,21 @@ struct DevBuf {
         if (p) (void)hipFree(p);
     }
 };
+
+// the context's scratch buffer with room for `bytes`; a buffer that grows is replaced (its contents are not kept) once
+// the work queued on the context's stream, which may still read it, has finished
+inline int reserve_scratch(spyhip_ctx* ctx, size_t bytes) {
+    if (bytes <= ctx->scratch_bytes) return 0;
+    if (ctx->scratch) {
+        SPY_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        (void)hipFree(ctx->scratch);
+        ctx->scratch = nullptr;
+        ctx->scratch_bytes = 0;
+    }
+    SPY_HIP_CHECK(hipMalloc(&ctx->scratch, bytes));
+    ctx->scratch_bytes = bytes;
+    return 0;
+}
 
 static inline int ilog2(unsigned v) {
     int l = 0;

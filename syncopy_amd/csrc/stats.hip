@@ -4,9 +4,9 @@
 
 namespace {
 
-unsigned elementwise_blocks(long long n) {
+unsigned elementwise_blocks(const spyhip_ctx* ctx, long long n) {
     long long blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
+    if (blocks > ctx->limits.elementwise_blocks) blocks = ctx->limits.elementwise_blocks;
     return (unsigned)(blocks < 1 ? 1 : blocks);
 }
 
@@ -16,7 +16,7 @@ extern "C" int spyhip_trial_sum(spyhip_ctx* ctx, const void* in_d, float* acc_d,
     if (!ctx || !in_d || !acc_d || ntrials < 0 || nfloat < 0) { spy::set_error("trial_sum: bad argument"); return -1; }
     if (ntrials == 0 || nfloat == 0) return 0;
     SPY_HIP_CHECK(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(spystat::trial_sum_kernel, dim3(elementwise_blocks(nfloat)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(spystat::trial_sum_kernel, dim3(elementwise_blocks(ctx, nfloat)), dim3(256), 0, ctx->stream,
                        reinterpret_cast<const float*>(in_d), acc_d, (long long)ntrials, (long long)nfloat);
     SPY_HIP_CHECK(hipGetLastError());
     return 0;
@@ -30,10 +30,10 @@ extern "C" int spyhip_trial_sum_finalize(spyhip_ctx* ctx, const float* acc_d, vo
     const long long nf = is_complex ? 2 * n : n;
     float* out = reinterpret_cast<float*>(mean_d);
     if (is_complex)
-        hipLaunchKernelGGL(spystat::trial_scale_kernel<true>, dim3(elementwise_blocks(nf)), dim3(256), 0, ctx->stream,
+        hipLaunchKernelGGL(spystat::trial_scale_kernel<true>, dim3(elementwise_blocks(ctx, nf)), dim3(256), 0, ctx->stream,
                            acc_d, out, (long long)ntotal, nf);
     else
-        hipLaunchKernelGGL(spystat::trial_scale_kernel<false>, dim3(elementwise_blocks(nf)), dim3(256), 0, ctx->stream,
+        hipLaunchKernelGGL(spystat::trial_scale_kernel<false>, dim3(elementwise_blocks(ctx, nf)), dim3(256), 0, ctx->stream,
                            acc_d, out, (long long)ntotal, nf);
     SPY_HIP_CHECK(hipGetLastError());
     return 0;
@@ -47,10 +47,10 @@ extern "C" int spyhip_trial_sqdev(spyhip_ctx* ctx, const void* in_d, const void*
     const float* in = reinterpret_cast<const float*>(in_d);
     const float* mean = reinterpret_cast<const float*>(mean_d);
     if (is_complex)
-        hipLaunchKernelGGL(spystat::trial_sqdev_kernel<true>, dim3(elementwise_blocks(n)), dim3(256), 0, ctx->stream, in,
+        hipLaunchKernelGGL(spystat::trial_sqdev_kernel<true>, dim3(elementwise_blocks(ctx, n)), dim3(256), 0, ctx->stream, in,
                            mean, acc_d, (long long)ntrials, (long long)n);
     else
-        hipLaunchKernelGGL(spystat::trial_sqdev_kernel<false>, dim3(elementwise_blocks(n)), dim3(256), 0, ctx->stream, in,
+        hipLaunchKernelGGL(spystat::trial_sqdev_kernel<false>, dim3(elementwise_blocks(ctx, n)), dim3(256), 0, ctx->stream, in,
                            mean, acc_d, (long long)ntrials, (long long)n);
     SPY_HIP_CHECK(hipGetLastError());
     return 0;
@@ -62,7 +62,7 @@ extern "C" int spyhip_trial_var_finalize(spyhip_ctx* ctx, const float* acc_d, vo
     if (n == 0) return 0;
     SPY_HIP_CHECK(hipSetDevice(ctx->device));
     float* out = reinterpret_cast<float*>(out_d);
-    const dim3 g(elementwise_blocks(n)), b(256);
+    const dim3 g(elementwise_blocks(ctx, n)), b(256);
     const long long T = ntotal, N = n;
     switch ((is_complex ? 2 : 0) + (take_sqrt ? 1 : 0)) {
         case 0: hipLaunchKernelGGL((spystat::trial_var_finalize_kernel<false, false>), g, b, 0, ctx->stream, acc_d, out, T, N); break;
@@ -78,7 +78,7 @@ extern "C" int spyhip_itc_accumulate(spyhip_ctx* ctx, const void* in_d, void* ac
     if (!ctx || !in_d || !acc_d || ntrials < 0 || n < 0) { spy::set_error("itc_accumulate: bad argument"); return -1; }
     if (ntrials == 0 || n == 0) return 0;
     SPY_HIP_CHECK(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(spystat::itc_accum_kernel, dim3(elementwise_blocks(n)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(spystat::itc_accum_kernel, dim3(elementwise_blocks(ctx, n)), dim3(256), 0, ctx->stream,
                        reinterpret_cast<const float2*>(in_d), reinterpret_cast<float2*>(acc_d), (long long)ntrials,
                        (long long)n);
     SPY_HIP_CHECK(hipGetLastError());
@@ -93,7 +93,7 @@ extern "C" int spyhip_itc_finalize(spyhip_ctx* ctx, const void* acc_d, float* ou
     }
     if (outer == 0 || inner == 0) return 0;
     SPY_HIP_CHECK(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(spystat::itc_finalize_kernel, dim3(elementwise_blocks(outer * inner)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(spystat::itc_finalize_kernel, dim3(elementwise_blocks(ctx, outer * inner)), dim3(256), 0, ctx->stream,
                        reinterpret_cast<const float2*>(acc_d), out_d, (long long)ntotal, (long long)outer,
                        (long long)ntaper, (long long)inner);
     SPY_HIP_CHECK(hipGetLastError());
@@ -105,7 +105,7 @@ extern "C" int spyhip_axis_nanvar(spyhip_ctx* ctx, const void* x_d, int64_t oute
     if (!ctx || !x_d || !out_d || outer < 1 || n < 1 || inner < 1) { spy::set_error("axis_nanvar: bad argument"); return -1; }
     SPY_HIP_CHECK(hipSetDevice(ctx->device));
     long long blocks = (outer * inner + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
+    if (blocks > ctx->limits.workgroups) blocks = ctx->limits.workgroups;
     const dim3 g((unsigned)blocks), b(256);
     const float* x = reinterpret_cast<const float*>(x_d);
     float* out = reinterpret_cast<float*>(out_d);
@@ -129,7 +129,7 @@ extern "C" int spyhip_axis_nanmedian(spyhip_ctx* ctx, const void* x_d, int64_t o
     const void* slices = x_d;
     if (inner > 1) {                    // slices contiguous first: (outer, n, inner) -> (outer, inner, n)
         const long long ntile = (long long)outer * ((n + 31) / 32) * ((inner + 31) / 32);
-        const unsigned tb = (unsigned)(ntile > 65535 ? 65535 : ntile);
+        const unsigned tb = (unsigned)(ntile > ctx->limits.workgroups ? ctx->limits.workgroups : ntile);
         if (is_complex)
             hipLaunchKernelGGL(spystat::axis_transpose_kernel<float2>, dim3(tb), dim3(256), 0, ctx->stream,
                                reinterpret_cast<const float2*>(x_d), reinterpret_cast<float2*>(work_d), (long long)outer,
@@ -142,7 +142,7 @@ extern "C" int spyhip_axis_nanmedian(spyhip_ctx* ctx, const void* x_d, int64_t o
         slices = work_d;
     }
     const long long nslice = (long long)outer * inner;
-    const unsigned mb = (unsigned)(nslice > 65535 ? 65535 : nslice);
+    const unsigned mb = (unsigned)(nslice > ctx->limits.workgroups ? ctx->limits.workgroups : nslice);
     if (is_complex)
         hipLaunchKernelGGL(spystat::axis_nanmedian_kernel<true>, dim3(mb), dim3(spystat::MED_THREADS), 0, ctx->stream,
                            reinterpret_cast<const float*>(slices), nslice, (long long)n, reinterpret_cast<float*>(out_d));

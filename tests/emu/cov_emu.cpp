@@ -1,30 +1,9 @@
-// CPU emulation of the covariance kernels (syncopy_amd/csrc/cov_kernel.h), TEST INFRASTRUCTURE ONLY (see hip_emu.h).
-// Launches the two kernels as cov.hip does, with the library's chunk of 32 rows and 2 waves per mean instead of 8.
-// Built by tests/test_timelock.py.
-#include "hip_emu.h"
+// CPU emulation of the channel covariance, TEST INFRASTRUCTURE ONLY (see hip_emu.h): the library's own launcher
+// (syncopy_amd/csrc/cov.hip) and kernels, on the runtime stand-in hip/hip_runtime.h.  Built by tests/test_timelock.py.
+#include "../../syncopy_amd/csrc/cov.hip"
+#include "emu_unit.h"
 
-namespace emu {
-thread_local dim3 t_threadIdx, t_blockIdx, t_blockDim, t_gridDim;
-thread_local BlockCtx* t_ctx = nullptr;
-}  // namespace emu
-
-#include "../../syncopy_amd/csrc/cov_kernel.h"
-
-namespace {
-constexpr int NW = 2, KC = 32;
-}  // namespace
-
-extern "C" {
-
-// mean: T * C doubles of work space; returns the number of workgroups of the covariance kernel per trial
-long long emu_cov(const float* x, double* mean, float* out, long long T, long long N, long long C, long long ddof) {
-    emu::launch(dim3((unsigned)((C + 63) / 64), (unsigned)T), dim3(64 * NW), 0,
-                [&] { spycov::cov_mean_kernel<NW>(x, mean, N, C); });
-    const double scale = 1.0 / (double)(N - ddof);
-    const long long blocks = spycov::cov_blocks(C);
-    emu::launch(dim3((unsigned)blocks, (unsigned)T), dim3(spycov::CovTile<KC>::THREADS), (size_t)spycov::CovTile<KC>::lds_bytes(),
-                [&] { spycov::cov_kernel<KC>(x, mean, out, N, C, scale); });
-    return blocks;
+// the same launcher with 2 waves per mean instead of 8 (the cases of test_emu_cov are tuned to it)
+extern "C" int emu_cov_small(spyhip_ctx* ctx, const float* x, float* out, int64_t ntrials, int64_t n, int64_t nchan, int64_t ddof) {
+    return cov_launch<2>(ctx, x, out, ntrials, n, nchan, ddof);
 }
-
-}  // extern "C"

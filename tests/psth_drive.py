@@ -3,11 +3,11 @@ inputs of the four kernels of csrc/psth_kernel.h from raw arrays or from a `_pla
 at the kernels' dispatch edges, and the emulator's driver."""
 import ctypes as C
 import os
-import subprocess
 import types
 
 import numpy as np
 
+import build_emu as BE
 import psth_oracle as PO
 import syncopy_amd as spy
 from syncopy_amd.statistics import spike_psth as SP
@@ -117,26 +117,10 @@ def edge_adversary(samplerate, exact, start=3_000_000_000):
 
 # ---- the emulator --------------------------------------------------------------------------------------------------
 def build_emu():
-    src = os.path.join(HERE, "emu", "psth_emu.cpp")
-    out = os.path.join(HERE, "emu", "_build", "libpsthemu.so")
-    csrc = os.path.join(HERE, "..", "syncopy_amd", "csrc")
-    deps = [src, os.path.join(HERE, "emu", "hip_emu.h"), os.path.join(csrc, "psth_kernel.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        cxx = clang if os.path.exists(clang) else "g++"
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-x", "c++", src, "-o", out])
-    lib = C.CDLL(out)
-    ll, vp, dbl = C.c_longlong, C.c_void_p, C.c_double
-    lib.emu_psth_tiles.argtypes = [vp] * 5
-    lib.emu_psth_presence.argtypes = [vp, vp, vp, vp, ll, ll, vp, ll, vp, ll, vp]
-    lib.emu_psth_presence.restype = None
-    lib.emu_psth_bin_rows.argtypes = [vp, vp, vp, vp, vp, ll, vp, ll, dbl, vp]
-    lib.emu_psth_bin_rows.restype = None
-    lib.emu_psth_count.argtypes = [vp, vp, vp, vp, ll, ll, vp, ll, ll, ll, dbl, vp]
-    lib.emu_psth_count.restype = ll
-    lib.emu_psth_proportion.argtypes = [vp, vp, vp, vp, vp, vp, ll, ll, vp, vp, ll, vp, ll, ll, ll, vp, vp]
-    lib.emu_psth_proportion.restype = None
+    """the library's own launchers of csrc/psth.hip on the CPU, with a context of default launch limits"""
+    lib = BE.emulated_library("psth")
+    lib.emu_psth_tiles.argtypes = [C.c_void_p] * 5
+    lib.ctx = BE.ctx(lib)
     return lib
 
 
@@ -156,9 +140,9 @@ def emu_presence(lib, table):
 
     def presence(pre):
         flags = np.zeros(pre.C * pre.U, dtype=np.uint8)
-        lib.emu_psth_presence(_p(chan), _p(unit), _p(pre.row_lo), _p(pre.row_hi), len(pre.row_lo),
-                              int((pre.row_hi - pre.row_lo).max()), _p(pre.chan_ok), pre.C, _p(pre.unit_ok), pre.U,
-                              _p(flags))
+        assert lib.spyhip_psth_presence(lib.ctx, _p(chan), _p(unit), _p(pre.row_lo), _p(pre.row_hi), len(pre.row_lo),
+                                        int((pre.row_hi - pre.row_lo).max()), _p(pre.chan_ok), pre.C, _p(pre.unit_ok),
+                                        pre.U, _p(flags)) == 0
         return flags
     return presence
 
@@ -169,16 +153,19 @@ def emu_histogram(lib, table, k):
     sample, chan, unit = _columns(table)
     T = len(k.row_lo)
     rows = np.full((T, k.nbins + 1), -(1 << 40), dtype=np.int64)
-    lib.emu_psth_bin_rows(_p(sample), _p(k.row_lo), _p(k.row_hi), _p(k.start), _p(k.onset), T, _p(k.edges), k.nbins + 1,
-                          k.samplerate, _p(rows))
+    assert lib.spyhip_psth_bin_rows(lib.ctx, _p(sample), _p(k.row_lo), _p(k.row_hi), _p(k.start), _p(k.onset), T,
+                                    _p(k.edges), k.nbins + 1, k.samplerate, _p(rows)) == 0
     assert np.all(rows >= k.row_lo[:, None]) and np.all(rows <= k.row_hi[:, None]) and np.all(np.diff(rows, axis=1) >= 0)
     out = np.full((T, k.nbins, k.ncols), -7.0, dtype=np.float32)
-    blocks = lib.emu_psth_count(_p(chan), _p(unit), _p(rows), _p(k.lut), k.C, k.U, _p(k.lohi), T, k.nbins, k.ncols,
-                                k.scale, _p(out))
-    assert blocks == T * -(-k.nbins // BIN_TILE) * -(-k.ncols // COL_TILE)
+    lib.emu_launch_log_reset()
+    assert lib.spyhip_psth_count(lib.ctx, _p(chan), _p(unit), _p(rows), _p(k.lut), k.C, k.U, _p(k.lohi), T, k.nbins,
+                                 k.ncols, k.scale, _p(out)) == 0
+    (grid,) = BE.launches(lib)[:, :3]
+    assert grid.prod() == T * -(-k.nbins // BIN_TILE) * -(-k.ncols // COL_TILE)
     if k.output == "proportion":
         S = np.full((T, k.nk), -9, dtype=np.int32)
-        lib.emu_psth_proportion(_p(chan), _p(unit), _p(k.row_lo), _p(k.row_hi), _p(rows), _p(k.lut), k.C, k.U,
-                                _p(k.unit_k), _p(k.col_k), k.nk, _p(k.edges), T, k.nbins, k.ncols, _p(S), _p(out))
+        assert lib.spyhip_psth_proportion(lib.ctx, _p(chan), _p(unit), _p(k.row_lo), _p(k.row_hi), _p(rows), _p(k.lut),
+                                          k.C, k.U, _p(k.unit_k), _p(k.col_k), k.nk, _p(k.edges), T, k.nbins, k.ncols,
+                                          _p(S), _p(out)) == 0
         assert np.all(S >= -1)
     return out.reshape(T * k.nbins, k.ncols)

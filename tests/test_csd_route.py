@@ -2,27 +2,17 @@
 syncopy_amd/csrc/csd_route.h, compiled with the host compiler alone (no HIP, no device) and asked through a small C shim
 (tests/emu/csd_route_shim.cpp).  The library and the kernel emulator both walk the steps this header returns."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "emu", "csd_route_shim.cpp")
-OUT = os.path.join(HERE, "emu", "_build", "libspycsdroute.so")
-HEADER = os.path.join(HERE, "..", "syncopy_amd", "csrc", "csd_route.h")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+import build_emu
+
 CAP = 4096
 
 
 @pytest.fixture(scope="module")
 def lib():
-    deps = [SHIM, HEADER, os.path.join(HERE, "emu", "emu_m3_widths.h")]
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        cxx = CLANG if os.path.exists(CLANG) else "g++"
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", SHIM, "-o", OUT])
-    lib = C.CDLL(OUT)
+    lib = build_emu.build_shim("csd_route_shim.cpp", "libspycsdroute.so")
     lib.csd_recut_main.restype = lib.csd_tri_tiles.restype = lib.csd_route_sweep.restype = C.c_longlong
     return lib
 

@@ -4,30 +4,22 @@ asked through a small C shim (tests/emu/cwt_route_shim.cpp).  The library and th
 header returns."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import build_emu
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "emu"))
-SHIM = os.path.join(HERE, "emu", "cwt_route_shim.cpp")
-OUT = os.path.join(HERE, "emu", "_build", "libspycwtroute.so")
-DEPS = [SHIM, os.path.join(HERE, "emu", "cwt_route_text.h"), os.path.join(HERE, "..", "syncopy_amd", "csrc", "cwt_route.h"),
-        os.path.join(HERE, "..", "syncopy_amd", "csrc", "host_fft.h")]
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 CAP = 1 << 16
 _dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in DEPS):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        cxx = CLANG if os.path.exists(CLANG) else "g++"
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", SHIM, "-o", OUT])
-    lib = C.CDLL(OUT)
+    lib = build_emu.build_shim("cwt_route_shim.cpp", "libspycwtroute.so")
     lib.cwt_route_sweep.restype = C.c_longlong
     return lib
 

@@ -1,16 +1,11 @@
 """Which kernel family serves a tapered FFT: the pure route of syncopy_amd/csrc/mtmfft_route.h, compiled with the host
 compiler alone (no HIP, no device) and asked through a small C shim."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "emu", "route_shim.cpp")
-OUT = os.path.join(HERE, "emu", "_build", "libspyroute.so")
-CSRC = os.path.join(HERE, "..", "syncopy_amd", "csrc")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+import build_emu
+
 
 OUTPUT = {"pow": 0, "abs": 1, "fourier": 2, "angle": 5}
 F32 = ["QUAD", "QUAD_HALF", "DEC", "DEC_HALF", "MIXED", "BLUE", "DECLONG", "LONG", "GENERIC"]
@@ -20,12 +15,7 @@ LDS = 160 * 1024
 
 @pytest.fixture(scope="module")
 def lib():
-    deps = [SHIM] + [os.path.join(CSRC, f) for f in ("mtmfft_route.h", "mtmfft_mixed_plan.h", "f64_plus_plan.h")]
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        cxx = CLANG if os.path.exists(CLANG) else "g++"
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", SHIM, "-o", OUT])
-    return C.CDLL(OUT)
+    return build_emu.build_shim("route_shim.cpp", "libspyroute.so")
 
 
 def route32(lib, nfft, output="pow", keep=True, nchan=5, ntaper=2, force=False, lds=LDS, nsig=None):

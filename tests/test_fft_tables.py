@@ -2,27 +2,17 @@
 return and the kernel emulator points its arguments at the same vectors (mtmfft_tables.h); here they are compiled with the
 host compiler alone (no HIP, no device) and asked through a small C shim."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "emu", "tables_shim.cpp")
-OUT = os.path.join(HERE, "emu", "_build", "libspytables.so")
-CSRC = os.path.join(HERE, "..", "syncopy_amd", "csrc")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+import build_emu
+
 
 
 @pytest.fixture(scope="module")
 def lib():
-    deps = [SHIM, os.path.join(CSRC, "host_fft.h")]
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        cxx = CLANG if os.path.exists(CLANG) else "g++"
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", SHIM, "-o", OUT])
-    return C.CDLL(OUT)
+    return build_emu.build_shim("tables_shim.cpp", "libspytables.so")
 
 
 def _ptr(a):

@@ -20,16 +20,11 @@ The size classes at the 160 KiB of LDS per workgroup of the MI355X (ZB = 16, ZM 
     417 ... 448, 481 ... 512 MFMA                        zinv64_mfma_kernel                 zchol_kernel
 """
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SHIM = os.path.join(HERE, "emu", "granger_route_shim.cpp")
-OUT = os.path.join(HERE, "emu", "_build", "libspygrangerroute.so")
-HEADER = os.path.join(HERE, "..", "syncopy_amd", "csrc", "granger_route.h")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+import build_emu
+
 KIB = 1024
 LDS = [160 * KIB, 64 * KIB]
 CD = 16                 # bytes of a complex128
@@ -37,12 +32,7 @@ CD = 16                 # bytes of a complex128
 
 @pytest.fixture(scope="module")
 def lib():
-    deps = [SHIM, HEADER]
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        cxx = CLANG if os.path.exists(CLANG) else "g++"
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", SHIM, "-o", OUT])
-    return C.CDLL(OUT)
+    return build_emu.build_shim("granger_route_shim.cpp", "libspygrangerroute.so")
 
 
 def _ask(fn, nout, *args):

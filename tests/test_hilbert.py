@@ -7,42 +7,29 @@ packed with it come out bit-identical to a run in which that sample IS zero (two
 transform: no arithmetic could make them independent of the partner's finite values), and within parity of the oracle
 on their own data."""
 import ctypes as C
-import os
 import importlib
-import subprocess
 
 import numpy as np
 import pytest
 import scipy.signal as sps
 
+import build_emu
 import hilbert_oracle as HO
 import syncopy_amd as spy
 from parity import assert_parity, excess
 from syncopy_amd.shared.errors import SPYTypeError, SPYValueError
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 pre_mod = importlib.import_module("syncopy_amd.preproc.preprocessing")      # (the package re-exports the function by this name)
-CSRC = os.path.join(HERE, "..", "syncopy_amd", "csrc")
 HOW = dict(compute_method="sequential", routine_classes=HO.HILBERT_OPS)
 KIND = {"abs": 1, "complex": 2, "real": 3, "imag": 4, "angle": 5, "absreal": 6, "absimag": 7}
 COPY, PACKED, BLUE, ANY64 = range(4)
 vp = C.c_void_p
 
 
-def _compile(src, out, headers):
-    deps = [src, os.path.join(HERE, "emu", "hip_emu.h")] + [os.path.join(CSRC, h) for h in headers]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        cxx = "/opt/rocm/lib/llvm/bin/clang++" if os.path.exists("/opt/rocm/lib/llvm/bin/clang++") else "g++"
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-x", "c++", src, "-o", out])
-    return C.CDLL(out)
-
-
 # ---- the route -----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def route():
-    lib = _compile(os.path.join(HERE, "emu", "hilbert_route_shim.cpp"),
-                   os.path.join(HERE, "emu", "_build", "libhilbertroute.so"), ["hilbert_route.h", "f64_plus_plan.h"])
+    lib = build_emu.build_shim("hilbert_route_shim.cpp", "libhilbertroute.so")
     ip = C.POINTER(C.c_int)
     lib.hilbert_route_query.argtypes = [C.c_longlong, ip, ip, ip, ip, ip, C.POINTER(C.c_longlong), ip, ip, C.c_char_p]
     lib.hilbert_grid_query.argtypes = [C.c_longlong, C.c_int, C.c_int, ip, ip, ip, C.POINTER(C.c_uint)]
@@ -121,19 +108,26 @@ def test_route_weights_and_grid(route):
 # ---- CPU emulation of hilbert_kernel.h -----------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def emu():
-    lib = _compile(os.path.join(HERE, "emu", "hilbert_emu.cpp"), os.path.join(HERE, "emu", "_build", "libhilbertemu.so"),
-                   ["hilbert_kernel.h", "hilbert_route.h", "fft2_device.h", "fft_device.h", "f64_stockham.h",
-                    "f64_plus_plan.h", "cd_math.h", "host_fft.h"])
-    lib.emu_hilbert.argtypes = [vp, vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_char_p]
+    """run(x, output): the library's own plan and launchers of csrc/hilbert.hip on the CPU.  The float64 family runs in
+    launches of 3 work arrays (several launches, as a long batch takes on the device) unless a context is given."""
+    lib = build_emu.emulated_library("hilbert")
+    three = build_emu.ctx(lib, any64_chunk=3)
 
-    def run(x, output):
+    def run(x, output, ctx=three, rc=0):
         x = np.ascontiguousarray(x, dtype=np.float32)
         out = np.full(x.shape, -7.0, dtype=np.complex64 if output == "complex" else np.float32)
         flag = np.zeros(x.shape[0], dtype=np.int32)
-        name = C.create_string_buffer(192)
-        rc = lib.emu_hilbert(x.ctypes.data, out.ctypes.data, flag.ctypes.data, *x.shape, KIND[output], name)
-        assert rc == 0, rc
-        return out, flag, name.value.decode()
+        plan = vp()
+        assert lib.spyhip_hilbert_plan_create(ctx, x.shape[1], C.byref(plan)) == 0
+        name = lib.spyhip_hilbert_plan_kernel_name(plan).decode()
+        if name.startswith("hilbert_packed_kernel<13,"):
+            pytest.skip("8192 points run 512 OS threads per block: not emulated")
+        got = lib.spyhip_hilbert_exec(plan, x.ctypes.data, out.ctypes.data, x.shape[0], x.shape[2], KIND.get(output, output),
+                                      flag.ctypes.data)
+        assert lib.spyhip_hilbert_plan_destroy(plan) == 0
+        assert got == rc, got
+        return out, flag, name
+    run.lib = lib
     return run
 
 
@@ -217,6 +211,25 @@ def test_emu_nan_contract(emu, n, bad):
         assert np.array_equal(got[keep].view(np.uint32), ref[keep].view(np.uint32))       # bit-identical partners
         others = [c for c in range(nchan) if c != 1]
         _check(got[:, :, others], x[:, :, others], output, f"N={n}, partners of the {bad} channel")
+
+
+@pytest.mark.parametrize("n", [4097, 4100])
+def test_emu_any64_chunks(emu, n):
+    """2 trials x 7 channels are 8 work arrays: three launches of at most 3, against the library's own chunk (one launch)"""
+    x = _trials(n, 7)
+    emu.lib.emu_launch_log_reset()
+    ref, _, _ = emu(x, "complex", ctx=build_emu.ctx(emu.lib))
+    got, flag, _ = emu(x, "complex")
+    assert [int(g) for g in build_emu.launches(emu.lib)[:, 0]] == [8, 3, 3, 2]
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)) and not flag.any()
+    _check(got, x, "complex", f"N={n} in chunks")
+
+
+def test_emu_refusals(emu):
+    x = _trials(16, 3)
+    for kind in (0, 8):                                     # an output kind outside SPYHIP_OUT_ABS ... SPYHIP_OUT_ABSIMAG
+        emu(x, kind, rc=-1)
+    assert emu.lib.spyhip_hilbert_exec(None, x.ctypes.data, x.ctypes.data, 2, 3, 1, x.ctypes.data) == -1
 
 
 # ---- the front end with the model table ------------------------------------------------------------------------------

@@ -3,15 +3,16 @@ front end driven by the NumPy / SciPy model (preproc_oracle.py), its argument ch
 kernels of syncopy_amd/csrc/preproc_kernel.h against the model."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import scipy.signal as sps
 
+import build_emu
 import syncopy_amd as spy
 import preproc_oracle as PO
 from parity import assert_parity
+from syncopy_amd._lib import SIGNATURES
 from syncopy_amd.preproc import design
 from syncopy_amd.shared.errors import SPYTypeError, SPYValueError
 
@@ -144,28 +145,21 @@ def test_input_errors_and_short_trials():
 # ---- CPU emulation of preproc_kernel.h ----------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(HERE, "emu", "preproc_emu.cpp")
-    out = os.path.join(HERE, "emu", "_build", "libpreprocemu.so")
-    csrc = os.path.join(HERE, "..", "syncopy_amd", "csrc")
-    deps = [src, os.path.join(HERE, "emu", "hip_emu.h"), os.path.join(csrc, "preproc_kernel.h"), os.path.join(csrc, "np_sum.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        cxx = clang if os.path.exists(clang) else "g++"
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-x", "c++", src, "-o", out])
-    lib = C.CDLL(out)
+    """the library's own launchers of csrc/preproc.hip on the CPU, with a context of default launch limits"""
+    lib = build_emu.emulated_library("preproc")
     i, vp = C.c_int, C.c_void_p
-    lib.emu_detrend.argtypes = [vp, vp, i, i, i, i, i, vp]
-    lib.emu_standardize.argtypes = [vp, vp, i, i, i, i, vp]
-    lib.emu_sosfilt.argtypes = [vp, vp, i, i, i, vp, i, i, vp]
-    lib.emu_sosfiltfilt.argtypes = [vp, vp, vp, i, i, i, vp, vp, i, i, i, vp]
     lib.model_sosfilt.argtypes = [vp, vp, vp, i, i, vp, vp, i, i, i]
-    lib.emu_fir_same.argtypes = [vp, vp, i, i, i, vp, i, i, vp]
+    lib.emu_fir_same_small.restype, lib.emu_fir_same_small.argtypes = SIGNATURES["spyhip_fir_same"]
+    lib.ctx = build_emu.ctx(lib)
     return lib
 
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _d(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def _batch(T, N, Cn, seed):
@@ -179,14 +173,14 @@ def test_emu_detrend_and_standardize(emu, shape):
     x[-1, 3, 0] = np.nan
     flag = np.zeros(shape[0], np.int32)
     out = np.empty_like(x)
-    emu.emu_detrend(_p(x), _p(out), *shape, 0, 0, _p(flag))
+    assert emu.spyhip_detrend(emu.ctx, _p(x), _p(out), *shape, 0, 0, _p(flag)) == 0
     for t in range(shape[0]):
         assert np.array_equal(out[t], PO.detrend(x[t], 0), equal_nan=True)           # NumPy's float32 order, bit for bit
     assert list(flag) == [0] * (shape[0] - 1) + [1]
-    emu.emu_standardize(_p(x), _p(out), *shape, 1, _p(flag))
+    assert emu.spyhip_standardize(emu.ctx, _p(x), _p(out), *shape, 1, _p(flag)) == 0
     for t in range(shape[0]):
         assert np.array_equal(out[t], np.abs(PO.standardize(x[t])), equal_nan=True)
-    emu.emu_detrend(_p(x), _p(out), *shape, 1, 0, _p(flag))
+    assert emu.spyhip_detrend(emu.ctx, _p(x), _p(out), *shape, 1, 0, _p(flag)) == 0
     for t in range(shape[0]):
         ref = PO.detrend(x[t], 1)
         ok = ~np.isnan(ref)
@@ -281,34 +275,82 @@ def test_emu_sos(emu, ftype, freq, order):
         shape = (2, nsamp, 3)
         x = _batch(*shape, seed=2)
         out = np.empty_like(x)
-        assert emu.emu_sosfilt(_p(x), _p(out), *shape, _p(sos), sos.shape[0], 0, _p(flag)) == 0
+        assert emu.spyhip_sosfilt(emu.ctx, _p(x), _p(out), *shape, _d(sos), sos.shape[0], 0, _p(flag)) == 0
         for t in range(2):
             ref = PO.sosfilt(x[t], sos)
             assert_parity(out[t], ref, what="sosfilt")
             assert sos_excess(out[t], ref) <= 1.0
         work = np.empty((2, nsamp + 2 * edge, 3))
-        assert emu.emu_sosfiltfilt(_p(x), _p(out), _p(work), *shape, _p(sos), _p(zi), sos.shape[0], edge, 1, _p(flag)) == 0
+        assert emu.spyhip_sosfiltfilt(emu.ctx, _p(x), _p(out), _p(work), *shape, _d(sos), _d(zi), sos.shape[0], edge, 1, _p(flag)) == 0
         for t in range(2):
             ref = np.abs(PO.sosfiltfilt(x[t], sos))
             assert_parity(out[t], ref, what="sosfiltfilt")
             assert sos_excess(out[t], ref) <= 1.0
         assert not flag.any()
-    # a trial of exactly `edge` samples and a 13th section are refused, as by the launchers
-    assert emu.emu_sosfiltfilt(_p(x), _p(out), _p(work), 2, edge, 3, _p(sos), _p(zi), sos.shape[0], edge, 1, _p(flag)) == -1
-    assert emu.emu_sosfilt(_p(x), _p(out), *shape, _p(sos), 13, 0, _p(flag)) == -1
+    # a trial of exactly `edge` samples and a 13th section are refused
+    assert emu.spyhip_sosfiltfilt(emu.ctx, _p(x), _p(out), _p(work), 2, edge, 3, _d(sos), _d(zi), sos.shape[0], edge, 1, _p(flag)) == -1
+    assert emu.spyhip_sosfilt(emu.ctx, _p(x), _p(out), *shape, _d(sos), 13, 0, _p(flag)) == -1
 
 
+def _fir(emu, fn, x, taps, ctx=None):
+    flag = np.zeros(x.shape[0], np.int32)
+    out = np.empty_like(x)
+    assert fn(ctx or emu.ctx, _p(x), _p(out), *x.shape, _p(taps), len(taps), 0, _p(flag)) == 0
+    return out, flag
+
+
+def _check_fir(x, taps, out):
+    for t in range(x.shape[0]):
+        ref = PO.fir64(x[t], taps)
+        ok = ~np.isnan(ref)
+        assert np.array_equal(np.isnan(out[t]), ~ok)
+        assert_parity(out[t][ok], ref[ok], what="fir")
+
+
+# a tile of 8 outputs, 8 taps per stage
 @pytest.mark.parametrize("N,Cn,ntaps", [(40, 3, 9), (33, 65, 17), (8, 2, 25), (23, 1, 8 + 1), (16, 4, 41)])
 def test_emu_fir(emu, N, Cn, ntaps):
     x = _batch(2, N, Cn, seed=3)
     x[1, N // 2, Cn - 1] = np.nan
     taps = np.random.default_rng(4).normal(size=ntaps)
-    flag = np.zeros(2, np.int32)
-    out = np.empty_like(x)
-    emu.emu_fir_same(_p(x), _p(out), 2, N, Cn, _p(taps), ntaps, 0, _p(flag))
-    for t in range(2):
-        ref = PO.fir64(x[t], taps)
-        ok = ~np.isnan(ref)
-        assert np.array_equal(np.isnan(out[t]), ~ok)
-        assert_parity(out[t][ok], ref[ok], what="fir")
+    out, flag = _fir(emu, emu.emu_fir_same_small, x, taps)
+    _check_fir(x, taps, out)
     assert list(flag) == [0, 1]
+
+
+# the library's tile: 128 outputs x 64 channels per workgroup, 128 taps per stage - one tile and one stage exactly, one
+# sample and one tap more, and two of each with one more
+@pytest.mark.parametrize("Cn", [64, 65])
+@pytest.mark.parametrize("N,ntaps", [(128, 128), (129, 129), (257, 257)])
+def test_emu_fir_library_tile(emu, N, ntaps, Cn):
+    x = _batch(2, N, Cn, seed=5)
+    x[1, N // 2, Cn - 1] = np.nan
+    taps = np.random.default_rng(6).normal(size=ntaps)
+    emu.emu_launch_log_reset()
+    out, flag = _fir(emu, emu.spyhip_fir_same, x, taps)
+    g = build_emu.launches(emu)
+    assert g.shape[0] == 1 and list(g[0, :3]) == [-(-Cn // 64), -(-N // 128), 2] and g[0, 3] == 512
+    _check_fir(x, taps, out)
+    assert list(flag) == [0, 1]
+
+
+def test_emu_fir_trial_chunks(emu):
+    """7 trials at 3 trials per launch: the offsets of input, output and flag in the loop over grid.z"""
+    x = _batch(7, 130, 3, seed=7)
+    x[5, 11, 1] = np.nan
+    taps = np.random.default_rng(8).normal(size=9)
+    ref, flag0 = _fir(emu, emu.spyhip_fir_same, x, taps)
+    emu.emu_launch_log_reset()
+    out, flag = _fir(emu, emu.spyhip_fir_same, x, taps, ctx=build_emu.ctx(emu, grid_yz=3))
+    assert [int(z) for z in build_emu.launches(emu)[:, 2]] == [3, 3, 1]
+    assert np.array_equal(out.view(np.uint32), ref.view(np.uint32))
+    assert list(flag) == list(flag0) == [0, 0, 0, 0, 0, 1, 0]
+    _check_fir(x, taps, out)
+
+
+def test_emu_refusals(emu):
+    x = _batch(2, 40, 3, seed=9)
+    out, flag, taps = np.empty_like(x), np.zeros(2, np.int32), np.ones(5)
+    assert emu.spyhip_standardize(emu.ctx, _p(x), _p(x), 2, 40, 3, 0, _p(flag)) == -1                       # in == out
+    assert emu.spyhip_fir_same(emu.ctx, _p(x), _p(x), 2, 40, 3, _p(taps), 5, 0, _p(flag)) == -1
+    assert emu.spyhip_fir_same(emu.ctx, _p(x), _p(out), 2, 40, 3, _p(taps), 5, 0, _p(flag)) == 0

@@ -70,6 +70,13 @@ def test_emu_tiles_are_the_headers(emu):
     assert [x.value for x in v] == [D.BIN_TILE, D.COL_TILE, D.UNIT_TILE, D.PROP_TILE, D.THREADS]
 
 
+def test_emu_refuses_more_units_with_a_column_than_units(emu):
+    z = np.zeros(8, dtype=np.int64)
+    args = lambda nk: [emu.ctx] + [D._p(z)] * 6 + [2, 3, D._p(z), D._p(z), nk, D._p(z), 1, 4, 2, D._p(z), D._p(z)]      # noqa: E731
+    assert emu.spyhip_psth_proportion(*args(4)) == -1              # nk > nunit = 3
+    assert emu.spyhip_psth_proportion(*args(0)) == -1
+
+
 @pytest.mark.parametrize("name", D.golden_names())
 def test_emu_kernels_match_reference(emu, name):
     tab, par, edges, cols = D.golden_case(name)

@@ -3,15 +3,16 @@ recorded results of the reference's resampling module, the front end driven by t
 CPU emulation of the kernel of syncopy_amd/csrc/resample_kernel.h against the model."""
 import ctypes as C
 import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+import build_emu
 import syncopy_amd as spy
 import resample_oracle as RO
 from parity import assert_parity, excess
+from syncopy_amd._lib import SIGNATURES
 from syncopy_amd.preproc import design
 from syncopy_amd.shared.errors import SPYTypeError, SPYValueError
 
@@ -167,19 +168,10 @@ def test_input_errors():
 # ---- CPU emulation of resample_kernel.h ---------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(HERE, "emu", "resample_emu.cpp")
-    out = os.path.join(HERE, "emu", "_build", "libresampleemu.so")
-    csrc = os.path.join(HERE, "..", "syncopy_amd", "csrc")
-    deps = [src, os.path.join(HERE, "emu", "hip_emu.h"), os.path.join(csrc, "resample_kernel.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        cxx = clang if os.path.exists(clang) else "g++"
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-x", "c++", src, "-o", out])
-    lib = C.CDLL(out)
-    ll, vp = C.c_longlong, C.c_void_p
-    lib.emu_upfirdn.argtypes = [vp, vp, ll, ll, ll, ll, vp, C.c_int, C.c_int, C.c_int]
-    lib.emu_upfirdn.restype = C.c_int
+    """the library's own launcher of csrc/resample.hip on the CPU, with a context of default launch limits"""
+    lib = build_emu.emulated_library("resample")
+    lib.emu_upfirdn_small.restype, lib.emu_upfirdn_small.argtypes = SIGNATURES["spyhip_upfirdn"]
+    lib.ctx = build_emu.ctx(lib)
     return lib
 
 
@@ -187,13 +179,25 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def _run(emu, x, taps, up, down, nout=None):
+SMALL, LIBRARY = (2, 8, (4, 1)), (8, 128, (8, 4, 1))        # waves, taps per chunk, outputs per lane to choose from
+
+
+def _run(emu, x, taps, up, down, nout=None, tiles=SMALL, ctx=None):
+    """(result, outputs per lane of the tile that ran, trials per launch).  The tile is read from the launch log: the
+    dynamic LDS of UpfirdnTile (csrc/resample_kernel.h) differs between the outputs per lane at one `down`."""
     T, N, Cn = x.shape
     nout = -(-N * up // down) if nout is None else nout
     out = np.full((T, nout, Cn), np.nan, dtype=np.float32)
     taps = np.ascontiguousarray(taps, dtype=np.float64)
-    r = emu.emu_upfirdn(_p(x), _p(out), T, N, Cn, nout, _p(taps), len(taps), up, down)
-    return out, r
+    emu.emu_launch_log_reset()
+    fn = emu.emu_upfirdn_small if tiles is SMALL else emu.spyhip_upfirdn
+    assert fn(ctx or emu.ctx, _p(x), _p(out), T, N, Cn, nout, _p(taps), len(taps), up, down) == 0
+    g = build_emu.launches(emu)
+    nt, kc, choices = tiles
+    lds = {r: max(((r - 1) * down + kc) * 64 * 4, nt * r * 64 * 8) for r in choices}
+    assert len(set(lds.values())) == len(choices) and len(set(g[:, 6])) == 1 and np.all(g[:, 3] == 64 * nt)
+    (r,) = [r for r in choices if lds[r] == g[0, 6]]
+    return out, r, [int(z) for z in g[:, 2]]
 
 
 def _batch(T, N, Cn, seed):
@@ -222,7 +226,7 @@ EMU_CASES = [s + (65,) for s in SHAPES] + [s + (c,) for s in (SHAPES[0], SHAPES[
 def test_emu_upfirdn(emu, up, down, N, ntaps, nchan):
     x = _batch(2, N, nchan, seed=up + down)
     taps = np.random.default_rng(ntaps).normal(size=ntaps)
-    got, r = _run(emu, x, taps, up, down)
+    got, r, _ = _run(emu, x, taps, up, down)
     assert r == (4 if 3 * down + 8 <= 32 else 1)
     for t in range(2):
         ref = RO.resample64(x[t], taps, up, down)
@@ -233,16 +237,50 @@ def test_emu_upfirdn(emu, up, down, N, ntaps, nchan):
 def test_emu_three_trials_single_output_and_decimation(emu):
     x = _batch(3, 7, 5, seed=1)
     taps = np.random.default_rng(2).normal(size=11)
-    got, _ = _run(emu, x, taps, 1, 7)                          # one output per trial
+    got, _, _ = _run(emu, x, taps, 1, 7)                          # one output per trial
     assert got.shape == (3, 1, 5)
     for t in range(3):
         assert_parity(got[t], RO.resample64(x[t], taps, 1, 7), what="nout 1")
     x = _batch(3, 45, 65, seed=3)
     for skip in (1, 4, 8, 9, 44, 45, 100):
-        got, _ = _run(emu, x, np.ones(1), 1, skip)
+        got, _, _ = _run(emu, x, np.ones(1), 1, skip)
         assert np.array_equal(got, x[:, ::skip]), skip
     taps = design.windowed_sinc("hamming", 20, 0.1)            # the decimating second pass of downsample with lpfreq
     for skip in (4, 1):                                        # skip 1: a plain "same" filter (resample_poly copies there)
-        got, _ = _run(emu, x, taps, 1, skip)
+        got, _, _ = _run(emu, x, taps, 1, skip)
         for t in range(3):
             assert_parity(got[t], RO.PO.fir64(x[t], taps)[::skip], what="decimating same")
+
+
+# the library's tiles: (R - 1) * down + 128 staged rows within 256 - the last `down` of 8 outputs per lane and the first of
+# 4, the last of 4 and the first of 1; 129 taps are one chunk of 128 and one tap of a second at up = 1
+@pytest.mark.parametrize("up", [1, 3])
+@pytest.mark.parametrize("down,outputs", [(18, 8), (19, 4), (42, 4), (43, 1)])
+def test_emu_upfirdn_library_tiles(emu, down, outputs, up):
+    x = _batch(2, 70, 65, seed=up + down)
+    taps = np.random.default_rng(129).normal(size=129)
+    got, r, _ = _run(emu, x, taps, up, down, tiles=LIBRARY)
+    assert r == outputs
+    for t in range(2):
+        # 3 / 18 and 3 / 42 share a factor, which resample_poly (RO.resample64) divides out before it filters: the
+        # reference is its own upfirdn expression on the pair as given, which IS resample64 on the reduced pairs
+        ref = RO.upfirdn64(x[t], taps, up, down)
+        if np.gcd(up, down) == 1:
+            same = RO.resample64(x[t], taps, up, down)          # (taps / up * up there: a rounding of the taps apart)
+            assert np.abs(ref - same).max() <= 1e-14 * np.abs(same).max()
+        assert got[t].shape == ref.shape
+        assert_parity(got[t], ref, what=f"upfirdn {up}/{down}, library tile")
+
+
+def test_emu_upfirdn_trial_chunks_and_refusal(emu):
+    """7 trials at 3 per launch: the offsets of input and output in the loop over grid.z"""
+    x = _batch(7, 70, 65, seed=11)
+    taps = np.random.default_rng(12).normal(size=129)
+    ref, _, z = _run(emu, x, taps, 3, 19, tiles=LIBRARY)
+    assert z == [7]
+    got, _, z = _run(emu, x, taps, 3, 19, tiles=LIBRARY, ctx=build_emu.ctx(emu, grid_yz=3))
+    assert z == [3, 3, 1]
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+    for t in range(7):
+        assert_parity(got[t], RO.resample64(x[t], taps, 3, 19), what="upfirdn in chunks of trials")
+    assert emu.spyhip_upfirdn(emu.ctx, _p(x), _p(x), 7, 70, 65, 12, _p(taps), 129, 3, 19) == -1         # in == out

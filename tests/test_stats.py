@@ -2,11 +2,11 @@
 argument checks, and a CPU emulation of the kernels of syncopy_amd/csrc/stats_kernel.h against NumPy."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import build_emu
 import syncopy_amd as spy
 import stats_oracle as SO
 from parity import assert_parity
@@ -132,21 +132,10 @@ def test_argument_errors():
 # ---- CPU emulation of stats_kernel.h ------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(HERE, "emu", "stats_emu.cpp")
-    out = os.path.join(HERE, "emu", "_build", "libstatsemu.so")
-    csrc = os.path.join(HERE, "..", "syncopy_amd", "csrc")
-    deps = [src, os.path.join(HERE, "emu", "hip_emu.h"), os.path.join(csrc, "stats_kernel.h"), os.path.join(csrc, "np_sum.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        cxx = clang if os.path.exists(clang) else "g++"
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-x", "c++", src, "-o", out])
-    lib = C.CDLL(out)
-    ll, vp = C.c_longlong, C.c_void_p
-    lib.emu_trial_var.argtypes = [vp, vp, vp, vp, ll, ll, C.c_int, C.c_int, ll]
-    lib.emu_itc.argtypes = [vp, vp, vp, ll, ll, ll, ll, ll]
-    lib.emu_axis_nanvar.argtypes = [vp, ll, ll, ll, C.c_int, C.c_int, vp]
-    lib.emu_axis_nanmedian.argtypes = [vp, ll, ll, ll, C.c_int, vp, vp, C.c_uint]
+    """the library's own launchers of csrc/stats.hip on the CPU.  ctx: default launch limits; few: 3 workgroups for the
+    median, variance and transposition launches and 2 for the element-wise ones, so that every grid-stride loop runs"""
+    lib = build_emu.emulated_library("stats")
+    lib.ctx, lib.few = build_emu.ctx(lib), build_emu.ctx(lib, workgroups=3, elementwise_blocks=2)
     return lib
 
 
@@ -158,18 +147,31 @@ def _split(shape, axis):
     return int(np.prod(shape[:axis])), shape[axis], int(np.prod(shape[axis + 1:]))
 
 
-def emu_trial_var(lib, x, take_sqrt, chunk=None):
+def _chunks(T, chunk):
+    return [(a, min(chunk or T, T - a)) for a in range(0, T, chunk or T)]
+
+
+def emu_trial_var(lib, x, take_sqrt, chunk=None, ctx=None):
+    """spy.var / spy.std over trials as backend.py composes them: sums in chunks of trials, the mean, squared deviations
+    in chunks, the finalisation"""
+    ctx = ctx or lib.ctx
     x = np.ascontiguousarray(x)
     T, shape = x.shape[0], x.shape[1:]
-    cplx = np.iscomplexobj(x)
+    cplx, n = int(np.iscomplexobj(x)), int(np.prod(shape))
     mean = np.zeros(shape, x.dtype)
     acc = np.zeros(shape, np.float32)
     out = np.empty(shape, x.dtype)
-    lib.emu_trial_var(_p(x), _p(mean), _p(acc), _p(out), T, int(np.prod(shape)), int(cplx), int(take_sqrt), chunk or T)
+    for a, k in _chunks(T, chunk):
+        assert lib.spyhip_trial_sum(ctx, _p(x[a:]), _p(mean), k, n * (2 if cplx else 1)) == 0
+    assert lib.spyhip_trial_sum_finalize(ctx, _p(mean), _p(mean), T, n, cplx) == 0
+    for a, k in _chunks(T, chunk):
+        assert lib.spyhip_trial_sqdev(ctx, _p(x[a:]), _p(mean), _p(acc), k, n, cplx) == 0
+    assert lib.spyhip_trial_var_finalize(ctx, _p(acc), _p(out), T, n, cplx, int(take_sqrt)) == 0
     return out
 
 
-def emu_itc(lib, x, taper_axis, chunk=None):
+def emu_itc(lib, x, taper_axis, chunk=None, ctx=None):
+    ctx = ctx or lib.ctx
     x = np.ascontiguousarray(x, dtype=np.complex64)
     T, shape = x.shape[0], x.shape[1:]
     outer, K, inner = _split(shape, taper_axis)
@@ -177,11 +179,14 @@ def emu_itc(lib, x, taper_axis, chunk=None):
     oshape = list(shape)
     oshape[taper_axis] = 1
     out = np.empty(oshape, np.float32)
-    lib.emu_itc(_p(x), _p(acc), _p(out), T, outer, K, inner, chunk or T)
+    for a, k in _chunks(T, chunk):
+        assert lib.spyhip_itc_accumulate(ctx, _p(x[a:]), _p(acc), k, outer * K * inner) == 0
+    assert lib.spyhip_itc_finalize(ctx, _p(acc), _p(out), T, outer, K, inner) == 0
     return out
 
 
-def emu_axis(lib, x, axis, op, nblocks=3):
+def emu_axis(lib, x, axis, op, ctx=None):
+    """the median on 3 workgroups unless a context is given (each walks several slices when there are more)"""
     x = np.ascontiguousarray(x)
     outer, n, inner = _split(x.shape, axis)
     oshape = list(x.shape)
@@ -190,9 +195,9 @@ def emu_axis(lib, x, axis, op, nblocks=3):
     cplx = int(np.iscomplexobj(x))
     if op == "median":
         work = np.empty_like(x)
-        lib.emu_axis_nanmedian(_p(x), outer, n, inner, cplx, _p(work), _p(out), nblocks)
+        assert lib.spyhip_axis_nanmedian(ctx or lib.few, _p(x), outer, n, inner, cplx, _p(work), _p(out)) == 0
     else:
-        lib.emu_axis_nanvar(_p(x), outer, n, inner, cplx, int(op == "std"), _p(out))
+        assert lib.spyhip_axis_nanvar(ctx or lib.ctx, _p(x), outer, n, inner, cplx, int(op == "std"), _p(out)) == 0
     return out
 
 
@@ -295,3 +300,57 @@ def test_emu_median_all_nan_and_duplicates(emu):
     assert np.array_equal(emu_axis(emu, y, 1, "median"), SO.axis_median(y, 1))
     z = np.array([[1 + 1j, 1 + 0j, 4, 5]], np.complex64)
     assert emu_axis(emu, z, 1, "median")[0, 0] == np.complex64(2.5 + 0.5j)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+def test_emu_elementwise_grid_stride(emu, cplx):
+    """1800 elements are 8 workgroups of 256: on 2 the trial and phase kernels walk their grid-stride loops"""
+    rng = np.random.default_rng(8)
+    x = rng.normal(size=(3, 2, 900)).astype(np.float32)
+    if cplx:
+        x = (x + 1j * rng.normal(size=x.shape)).astype(np.complex64)
+    for take_sqrt in (0, 1):
+        emu.emu_launch_log_reset()
+        ref = emu_trial_var(emu, x, take_sqrt, 2)
+        assert set(build_emu.launches(emu)[:, 0]) == ({8, 15} if cplx else {8})
+        got = emu_trial_var(emu, x, take_sqrt, 2, ctx=emu.few)
+        assert set(build_emu.launches(emu)[:, 0]) == {2}
+        assert np.array_equal(_bits(got), _bits(ref))
+        assert_parity(got, (SO.trial_std if take_sqrt else SO.trial_var)(list(x)), what="trial var")
+    if cplx:
+        z = x.reshape(3, 2, 3, 300)
+        ref = emu_itc(emu, z, 1, 2)
+        got = emu_itc(emu, z, 1, 2, ctx=emu.few)
+        assert set(build_emu.launches(emu)[:, 0]) == {8, 3, 2}
+        assert np.array_equal(_bits(got), _bits(ref))
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+def test_emu_axis_workgroup_limit(emu, cplx):
+    """more slices and tiles than workgroups: 1600 slices are 7 workgroups of the variance kernel, (7, 5, 2) along axis 1
+    is 7 tiles of the transposition and 14 slices of the median - each on 3 workgroups, against the default limits"""
+    rng = np.random.default_rng(9)
+    x = _edge(rng, (40, 3, 40), cplx)
+    for op in ("var", "std"):
+        emu.emu_launch_log_reset()
+        ref = emu_axis(emu, x, 1, op)
+        got = emu_axis(emu, x, 1, op, ctx=emu.few)
+        assert [int(g) for g in build_emu.launches(emu)[:, 0]] == [7, 3]
+        assert np.array_equal(_bits(got), _bits(ref))
+    y = _edge(rng, (7, 5, 2), cplx)
+    emu.emu_launch_log_reset()
+    ref = emu_axis(emu, y, 1, "median", ctx=emu.ctx)
+    got = emu_axis(emu, y, 1, "median", ctx=emu.few)
+    assert [int(g) for g in build_emu.launches(emu)[:, 0]] == [7, 14, 3, 3]
+    assert np.array_equal(_bits(got), _bits(ref))
+    assert np.array_equal(got, SO.axis_median(y, 1), equal_nan=True)
+
+
+def test_emu_refusals(emu):
+    x = np.zeros((2, 3), np.float32)
+    assert emu.spyhip_axis_nanmedian(emu.ctx, _p(x), 1, 2, 3, 0, None, _p(x)) == -1        # inner > 1 without a work buffer
+    assert emu.spyhip_trial_sum_finalize(emu.ctx, _p(x), _p(x), 0, 6, 0) == -1             # no trial

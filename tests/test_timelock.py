@@ -1,18 +1,17 @@
 """spy.timelockanalysis without a GPU: its argument checks, the front end driven by the NumPy model (timelock_oracle.py),
 and a CPU emulation of the covariance kernels of syncopy_amd/csrc/cov_kernel.h against the model."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import build_emu
 import syncopy_amd as spy
 import timelock_oracle as TO
 from parity import assert_parity
+from syncopy_amd._lib import SIGNATURES
 from syncopy_amd.shared.errors import SPYTypeError, SPYValueError
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 HOW = dict(compute_method="sequential", routine_classes=TO.TIMELOCK_OPS)
 
 
@@ -226,30 +225,28 @@ def test_container_still_refused(tmp_path):
 # ---- CPU emulation of cov_kernel.h --------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(HERE, "emu", "cov_emu.cpp")
-    out = os.path.join(HERE, "emu", "_build", "libcovemu.so")
-    csrc = os.path.join(HERE, "..", "syncopy_amd", "csrc")
-    deps = [src, os.path.join(HERE, "emu", "hip_emu.h"), os.path.join(csrc, "cov_kernel.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-        cxx = clang if os.path.exists(clang) else "g++"
-        subprocess.check_call([cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-x", "c++", src, "-o", out])
-    lib = C.CDLL(out)
-    ll, vp = C.c_longlong, C.c_void_p
-    lib.emu_cov.argtypes = [vp, vp, vp, ll, ll, ll, ll]
-    lib.emu_cov.restype = ll
+    """the library's own launcher of csrc/cov.hip on the CPU, with a context of default launch limits"""
+    lib = build_emu.emulated_library("cov")
+    lib.emu_cov_small.restype, lib.emu_cov_small.argtypes = SIGNATURES["spyhip_cov_f32"]
+    lib.ctx = build_emu.ctx(lib)
     return lib
 
 
-def _run(emu, x, ddof):
+def _run(emu, x, ddof, fn=None, ctx=None, waves=2):
+    """(covariances, column means) of the launcher `fn` (default: the one with 2 waves per mean); the grids of the two
+    kernels are read from the launch log"""
     T, N, Cn = x.shape
+    ctx = ctx or emu.ctx
     out = np.full((T, Cn, Cn), -7.0, dtype=np.float32)
-    mean = np.full((T, Cn), np.nan)
     p = lambda a: a.ctypes.data_as(C.c_void_p)          # noqa: E731
-    blocks = emu.emu_cov(p(x), p(mean), p(out), T, N, Cn, 1 if ddof is None else ddof)
+    emu.emu_launch_log_reset()
+    assert (fn or emu.emu_cov_small)(ctx, p(x), p(out), T, N, Cn, 1 if ddof is None else ddof) == 0
+    g = build_emu.launches(emu)
     nb = -(-Cn // 64)
-    assert blocks == nb * (nb + 1) // 2
+    assert np.all(g[1::2, 0] == nb * (nb + 1) // 2)                     # workgroups of the covariance kernel per trial
+    assert np.all(g[0::2, 0] == nb) and np.all(g[0::2, 3] == 64 * waves) and g[:, 1].sum() == 2 * T
+    per = g[0, 1]                                                       # trials of a launch: the means of the last one
+    mean = np.ctypeslib.as_array(C.cast(emu.emu_ctx_scratch(ctx), C.POINTER(C.c_double)), (per, Cn))[:g[-1, 1]].copy()
     return out, mean
 
 
@@ -294,3 +291,29 @@ def test_emu_cov_nan_stays_in_its_row_and_column(emu):
         mask[:, bad] = True
         assert np.array_equal(np.isnan(got[t]), mask), t
         assert_cov(got[t], TO.cov(x[t]), what=f"NaN trial {t}")
+
+
+@pytest.mark.parametrize("ddof", [0, 1])
+@pytest.mark.parametrize("n,nchan", [(33, 65), (8, 1)])
+def test_emu_cov_library_waves(emu, n, nchan, ddof):
+    """8 waves per mean, as the library launches: more waves than rows (8, 1), and rows that do not divide by them"""
+    x = _batch(2, n, nchan, seed=nchan + n)
+    got, mean = _run(emu, x, ddof, fn=emu.spyhip_cov_f32, waves=8)
+    assert np.allclose(mean, x.astype(np.float64).mean(axis=1), rtol=1e-13, atol=0)
+    for t in range(2):
+        assert_cov(got[t], TO.cov(x[t], ddof), what=f"cov c={nchan} n={n} ddof={ddof} trial {t}")
+        assert np.array_equal(got[t], got[t].T)
+
+
+def test_emu_cov_trial_chunks_and_refusals(emu):
+    """7 trials at 3 per launch: the offsets of input, output and the mean scratch in the loop over grid.y"""
+    x = _batch(7, 33, 65, seed=8)
+    ref, _ = _run(emu, x, 1, fn=emu.spyhip_cov_f32, waves=8)
+    few = build_emu.ctx(emu, grid_yz=3)
+    got, mean = _run(emu, x, 1, fn=emu.spyhip_cov_f32, ctx=few, waves=8)
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+    assert np.allclose(mean, x[6:].astype(np.float64).mean(axis=1), rtol=1e-13, atol=0)     # the last launch: trial 6
+    p = lambda a: a.ctypes.data_as(C.c_void_p)          # noqa: E731
+    for ddof in (33, 34):                                                                   # ddof >= n
+        assert emu.spyhip_cov_f32(emu.ctx, p(x), p(got), 7, 33, 65, ddof) == -1
+    assert emu.spyhip_cov_f32(emu.ctx, p(x), p(x), 7, 33, 65, 1) == -1                      # in == out
