@@ -583,6 +583,44 @@ int spyhip_psth_proportion(spyhip_ctx* ctx, const int32_t* chan_d, const int32_t
                            const double* edges_d, int64_t ntrials, int64_t nbins, int64_t ncols, int32_t* s_d,
                            float* out_d);
 
+/* ---- operator arithmetic on data objects (datatype/arithmetic.py; datatype/methods/arithmetic.py: arithmetic_cF).
+ * out = a (op) b, element by element, over the selected trials of a data object, in one launch.  A tensor is a matrix of
+ * rows (time is the slowest axis of every data class) of `width` elements; `desc` holds four int64 per trial: the first
+ * output row, the first base row, the first row of a full-tensor operand, and the trial's rows.  The output rows of the
+ * trials follow each other (the result is stacked); the base rows may repeat, overlap and come in any order, which is
+ * all that a trial selection, a repeated trial or a latency window needs.  desc is the host copy, which is checked
+ * against a_rows, b_rows and out_rows (the tensors' row counts) before anything runs, desc_d the same table on the device.
+ * chan / chan_d (host and device copy, or both NULL): nchan_out indices < nchan_in, a channel selection of the base whose
+ * rows then have width / nchan_out * nchan_in elements (the channel axis is the fastest one).
+ * The base is read as a_type and converted to out_type in the load: float32 -> any, float64 -> float64 / complex128,
+ * complex64 -> complex64 / complex128, complex128 -> complex128.  The operand is of out_type already:
+ *   mode SPYHIP_ARITH_SCALAR: b_re + i b_im, by value (rounded to out_type first, as NumPy does);
+ *   mode SPYHIP_ARITH_BCAST : b_d, an array of b_rows ELEMENTS seen through a view of the trial's shape: the trial is
+ *                             (rows, b_extent[1], b_extent[2], b_extent[3]) with b_extent[1..3] multiplying to width,
+ *                             b_stride[0..3] the array's element stride along each axis, 0 where it broadcasts
+ *                             (b_extent[0]: its rows, if b_stride[0] != 0: no trial may have more);
+ *   mode SPYHIP_ARITH_FULL  : b_d, a tensor of b_rows rows of width elements, its trials' rows in desc.
+ * Real arithmetic is IEEE: + - * /, the correctly rounded square root; no fast-math.  Complex products are the textbook
+ * four multiplications (the compiler may fuse them), complex quotients NumPy's (Smith's method); float32 powers are
+ * float64 powers rounded once.  SPYHIP_ARITH_RSUB / _RDIV are b - a and b / a; _SQUARE, _COPY, _ONES and _SQRT take no
+ * operand (mode SCALAR) and are NumPy's fast paths of ** 2, 1, 0 and 0.5 (_COPY is also the cast); powers, squares, ones
+ * and roots exist for the real types only, the reflected operations not for mode FULL: -1 for what is not provided.
+ * Where every trial starts on a 16-byte boundary of the base, the result and the operand tensor, and there is no channel
+ * selection, a lane moves 16 bytes of the base at a time, else single elements.  Asynchronous on the context's stream;
+ * nothing is allocated; out_d must be neither a_d nor b_d. */
+enum spyhip_arith_op {
+    SPYHIP_ARITH_ADD = 0, SPYHIP_ARITH_SUB = 1, SPYHIP_ARITH_MUL = 2, SPYHIP_ARITH_DIV = 3, SPYHIP_ARITH_RSUB = 4,
+    SPYHIP_ARITH_RDIV = 5, SPYHIP_ARITH_POW = 6, SPYHIP_ARITH_SQUARE = 7, SPYHIP_ARITH_COPY = 8, SPYHIP_ARITH_ONES = 9,
+    SPYHIP_ARITH_SQRT = 10
+};
+enum spyhip_arith_mode { SPYHIP_ARITH_SCALAR = 0, SPYHIP_ARITH_BCAST = 1, SPYHIP_ARITH_FULL = 2 };
+enum spyhip_arith_type { SPYHIP_ARITH_F32 = 0, SPYHIP_ARITH_F64 = 1, SPYHIP_ARITH_C64 = 2, SPYHIP_ARITH_C128 = 3 };
+int spyhip_arith(spyhip_ctx* ctx, int op, int mode, int a_type, int out_type, const void* a_d, int64_t a_rows,
+                 const void* b_d, int64_t b_rows, const int64_t* b_extent, const int64_t* b_stride, double b_re,
+                 double b_im, const int64_t* desc, const int64_t* desc_d, int64_t ntrials, int64_t width,
+                 const int32_t* chan, const int32_t* chan_d, int64_t nchan_out, int64_t nchan_in, void* out_d,
+                 int64_t out_rows);
+
 #ifdef __cplusplus
 }
 #endif

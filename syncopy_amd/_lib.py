@@ -122,6 +122,9 @@ SIGNATURES = {
                                     C.c_double, vp]),
     "spyhip_psth_proportion": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp,
                                          C.c_int64, C.c_int64, C.c_int64, vp, vp]),
+    "spyhip_arith": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, c_i64p, c_i64p,
+                               C.c_double, C.c_double, c_i64p, vp, C.c_int64, C.c_int64, c_i32p, vp, C.c_int64, C.c_int64,
+                               vp, C.c_int64]),
 }
 
 

@@ -309,6 +309,69 @@ class Device:
             for b in bufs:
                 b.free()
 
+    # ---- operator arithmetic on data objects
+    def arith(self, op, base, trials, operand=0.0, operand_trials=None, channels=None, dtype=None):
+        """`trial (op) operand` for the trials of `base` (rows x ..., float32 / float64 / complex64 / complex128), stacked:
+        `trials` (T, 2) are [start, stop) rows, `op` one of 'add', 'sub', 'mul', 'div', 'rsub', 'rdiv' (operand - trial,
+        operand / trial), 'pow' and the one-argument 'square', 'copy', 'ones', 'sqrt'.  `operand`: a scalar, an array that
+        broadcasts to every trial, or with `operand_trials` (T, 2) a second matrix whose trials pair up with the base's.
+        `channels`: indices into the last axis of `base`; `dtype`: the result type (default: NumPy's for base and operand).
+        See spyhip_arith in include/spyhip.h."""
+        from .datatype.arithmetic import ARITH_OP, ARITH_TYPE, arith_view
+        base = np.ascontiguousarray(base)
+        trl = np.asarray(trials, dtype=np.int64).reshape(-1, 2)
+        n = trl[:, 1] - trl[:, 0]
+        if base.ndim < 1 or base.ndim > 4 or np.any(n < 0) or np.any(trl[:, 0] < 0) or np.any(trl[:, 1] > base.shape[0]):
+            raise ValueError("base must have 1 to 4 dimensions and hold the rows of every trial")
+        starts = np.concatenate(([0], np.cumsum(n))).astype(np.int64)
+        array = None if np.isscalar(operand) else np.asarray(operand)
+        if dtype is None:
+            dtype = np.result_type(base.dtype, operand if array is None else array.dtype)
+        dtype = np.dtype(dtype)
+        chan = None if channels is None else np.ascontiguousarray(channels, dtype=np.int32)
+        inner = base.shape[1:] if chan is None else base.shape[1:-1] + (chan.size,)
+        brow, mode, scalar, extent, stride, b_rows = starts[:-1], 0, 0.0, None, None, 0
+        bufs = []
+        try:
+            if array is None:
+                scalar = operand
+            elif operand_trials is None:
+                array = np.ascontiguousarray(array, dtype=dtype)
+                extent, stride = arith_view(array.shape, inner)
+                mode, b_rows = 1, array.size
+            else:
+                array = np.ascontiguousarray(array, dtype=dtype)
+                otrl = np.asarray(operand_trials, dtype=np.int64).reshape(-1, 2)
+                if array.shape[1:] != inner or not np.array_equal(otrl[:, 1] - otrl[:, 0], n):
+                    raise ValueError("the operand's trials must have the shapes of the base's")
+                brow, mode, b_rows = otrl[:, 0], 2, array.shape[0]
+            desc = np.ascontiguousarray(np.stack([starts[:-1], trl[:, 0], brow, n], axis=1))
+            a_d = self._put(base, base.dtype)
+            bufs.append(a_d)
+            out = Buffer(self, (int(starts[-1]),) + tuple(inner), dtype)
+            bufs.append(out)
+            if out.nbytes == 0:
+                return np.empty(out.shape, dtype=dtype)
+            b_d = None
+            if array is not None:
+                b_d = self._put(array, dtype)
+                bufs.append(b_d)
+            desc_d, chan_d = self._put(desc, np.int64), None if chan is None else self._put(chan, np.int32)
+            bufs += [desc_d] + ([] if chan_d is None else [chan_d])
+            i64p = lambda x: None if x is None else x.ctypes.data_as(_lib.c_i64p)      # noqa: E731
+            check(self.lib.spyhip_arith(self.handle, ARITH_OP[op], mode, ARITH_TYPE[base.dtype], ARITH_TYPE[dtype], a_d.ptr,
+                                        base.shape[0], None if b_d is None else b_d.ptr, b_rows, i64p(extent), i64p(stride),
+                                        float(np.real(scalar)), float(np.imag(scalar)), i64p(desc), desc_d.ptr,
+                                        desc.shape[0], int(np.prod(inner, dtype=np.int64)),
+                                        None if chan is None else chan.ctypes.data_as(_lib.c_i32p),
+                                        None if chan_d is None else chan_d.ptr, int(inner[-1]) if inner else 1,
+                                        int(base.shape[-1]), out.ptr, out.shape[0]), "spyhip_arith")
+            return out.numpy()
+        finally:
+            self.synchronize()
+            for b in bufs:
+                b.free()
+
     def close(self):
         if self.handle is not None:
             self.lib.spyhip_ctx_destroy(self.handle)

@@ -1456,3 +1456,47 @@ def psth_proportion(chan, unit, row_lo, row_hi, rows, lut, nchan, nunit, unit_k,
                                          _ptr(lut), int(nchan), int(nunit), _ptr(unit_k), _ptr(col_k), int(nk),
                                          _ptr(edges), T, nbins, ncols, _ptr(work), _ptr(out)), "spyhip_psth_proportion")
     return out
+
+
+# ---- operator arithmetic on data objects (csrc/arith.hip) -----------------------------------------------------------
+from .datatype.arithmetic import ARITH_OP, ARITH_TYPE, arith_view  # noqa: E402  (NumPy only: abi.py shares them)
+
+
+def arith(op, a, desc, out, scalar=0.0, array=None, operand=None, chan=None):
+    """out = a (op) operand over the trials of `desc` ((ntrials, 4) int64 on the host: output row, base row, operand row,
+    rows; see include/spyhip.h: spyhip_arith), one launch.  a, out: contiguous tensors whose first axis are the rows; the
+    base is converted to out's dtype in the load.  The operand is `scalar`, or `array` (contiguous, out's dtype, of a shape
+    that broadcasts to a trial), or `operand` (a tensor like out, with its own rows).  chan: channel indices into a's last
+    axis (out's last axis has len(chan) entries)."""
+    assert a.is_cuda and out.is_cuda and a.is_contiguous() and out.is_contiguous() and 1 <= a.dim() == out.dim() <= 4
+    desc = np.ascontiguousarray(desc, dtype=np.int64).reshape(-1, 4)
+    if desc.shape[0] == 0 or out.numel() == 0:
+        return out
+    width = int(np.prod(out.shape[1:], dtype=np.int64))
+    extent = stride = None
+    b, b_rows, mode = None, 0, 0
+    if array is not None:
+        assert array.is_cuda and array.is_contiguous() and array.dtype == out.dtype
+        extent, stride = arith_view(tuple(array.shape), tuple(out.shape[1:]))
+        b, b_rows, mode = array, int(array.numel()), 1
+    elif operand is not None:
+        assert operand.is_cuda and operand.is_contiguous() and operand.dtype == out.dtype
+        assert tuple(operand.shape[1:]) == tuple(out.shape[1:])
+        b, b_rows, mode = operand, int(operand.shape[0]), 2
+    chan_h = chan_d = None
+    if chan is not None:
+        chan_h = np.ascontiguousarray(chan, dtype=np.int32)
+        assert out.shape[-1] == chan_h.size and tuple(a.shape[1:-1]) == tuple(out.shape[1:-1])
+        chan_d = torch.from_numpy(chan_h).to(a.device)
+    else:
+        assert tuple(a.shape[1:]) == tuple(out.shape[1:])
+    desc_d = torch.from_numpy(desc).to(a.device)
+    ctx = _stat_ctx(a)
+    i64p = lambda x: None if x is None else x.ctypes.data_as(_lib.c_i64p)      # noqa: E731
+    check(ctx.lib.spyhip_arith(ctx.handle, ARITH_OP[op], mode, ARITH_TYPE[np.dtype(_NP_DTYPE[a.dtype])],
+                               ARITH_TYPE[np.dtype(_NP_DTYPE[out.dtype])], _ptr(a), int(a.shape[0]), _ptr(b), b_rows,
+                               i64p(extent), i64p(stride), float(np.real(scalar)), float(np.imag(scalar)), i64p(desc),
+                               _ptr(desc_d), desc.shape[0], width,
+                               None if chan_h is None else chan_h.ctypes.data_as(_lib.c_i32p), _ptr(chan_d),
+                               int(out.shape[-1]), int(a.shape[-1]), _ptr(out), int(out.shape[0])), "spyhip_arith")
+    return out

@@ -17,6 +17,11 @@ from ..shared.errors import SPYTypeError, SPYValueError
 from ..shared.tools import best_match
 
 
+def _process_operator(obj1, obj2, operator):
+    from .arithmetic import _process_operator as run
+    return run(obj1, obj2, operator)
+
+
 class _Base:
     _defaultDimord = None
 
@@ -41,6 +46,37 @@ class _Base:
     def _stackingDim(self):
         return 0
 
+    # ---- operators: everything happens in arithmetic._process_operator (datatype/base_data.py:1263-1288).  NumPy leaves
+    # `array - obj` and `np.float64(2) / obj` to the reflected methods instead of looping over the array's elements.
+    __array_ufunc__ = None
+
+    def __add__(self, other):
+        return _process_operator(self, other, "+")
+
+    def __radd__(self, other):
+        return _process_operator(other, self, "+")
+
+    def __sub__(self, other):
+        return _process_operator(self, other, "-")
+
+    def __rsub__(self, other):
+        return _process_operator(other, self, "-")
+
+    def __mul__(self, other):
+        return _process_operator(self, other, "*")
+
+    def __rmul__(self, other):
+        return _process_operator(other, self, "*")
+
+    def __truediv__(self, other):
+        return _process_operator(self, other, "/")
+
+    def __rtruediv__(self, other):
+        return _process_operator(other, self, "/")
+
+    def __pow__(self, other):
+        return _process_operator(self, other, "**")
+
     @property
     def data(self):
         if self._data is None and self._pending is not None:
@@ -64,6 +100,7 @@ class _Base:
         self._device = None
         self._device_key = None
         self._looks = {}                  # what precision="auto" measured on this array (CrossSpectra.needs_float64)
+        self._resident = None             # device tensor behind a pending result of the operators (arithmetic.py)
 
     def set_pending(self, thunk, shape, dtype):
         """The host array is `thunk()` - evaluated only if somebody reads `.data`."""
