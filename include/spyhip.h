@@ -621,6 +621,29 @@ int spyhip_arith(spyhip_ctx* ctx, int op, int mode, int a_type, int out_type, co
                  const int32_t* chan, const int32_t* chan_d, int64_t nchan_out, int64_t nchan_in, void* out_d,
                  int64_t out_rows);
 
+/* ---- data selection (datatype/selectdata.py; datatype/methods/selectdata.py: DataSelection, _selectdata).
+ * out = the selected rows of a tensor, of every row the selected elements, stacked and contiguous, in one launch.  The
+ * source is src_rows rows (time is the slowest axis of every data class) of extent[0] x extent[1] x extent[2] elements of
+ * elem_bytes bytes (4, 8 or 16), C-order; elements move as raw bits, so NaN payloads and signed zeros arrive unchanged.
+ * `desc` holds three int64 per trial: the first output row, the first source row and the trial's rows.  The output rows
+ * of the trials follow each other; the source rows may repeat, overlap and come in any order, and a trial may have no
+ * rows.  Inner axis i is taken whole (kind[i] = SPYHIP_SELECT_WHOLE), as the range [start[i], start[i] + count[i])
+ * (_RANGE) or through count[i] int32 indices (_LIST), unsorted and repeated as they come; the lists of the LIST axes
+ * follow each other in idx, in axis order.  desc and idx are the host copies, which are checked before anything runs,
+ * desc_d and idx_d the same tables on the device (idx and idx_d both NULL without a list).  -1 for an element size other
+ * than 4, 8 or 16, an output that is or overlaps the source, a trial outside src_rows or out_rows, output rows that
+ * are not stacked, an index or a range outside its extent, and a count of 0.
+ * Adjacent whole axes collapse (a selection of rows alone moves one contiguous run per trial).  A lane moves 16 bytes
+ * where the length of the innermost contiguous run and every run's byte offset in both tensors (the base addresses
+ * included) are multiples of 16, else one element; an index list on the fastest axis always means element lanes.  Lists
+ * of up to 4096 entries in all are read from LDS, longer ones from global memory.  Asynchronous on the context's stream;
+ * nothing is allocated, no atomics. */
+enum spyhip_select_kind { SPYHIP_SELECT_WHOLE = 0, SPYHIP_SELECT_RANGE = 1, SPYHIP_SELECT_LIST = 2 };
+int spyhip_select(spyhip_ctx* ctx, int elem_bytes, const void* src_d, int64_t src_rows, const int64_t* extent,
+                  const int32_t* kind, const int64_t* start, const int64_t* count, const int32_t* idx,
+                  const int32_t* idx_d, const int64_t* desc, const int64_t* desc_d, int64_t ntrials, void* out_d,
+                  int64_t out_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,8 @@ _LAZY = {"freqanalysis": ".specest.freqanalysis", "connectivityanalysis": ".conn
          "mean": ".statistics.summary_stats", "var": ".statistics.summary_stats", "std": ".statistics.summary_stats",
          "median": ".statistics.summary_stats", "itc": ".statistics.summary_stats",
          "preprocessing": ".preproc.preprocessing", "resampledata": ".preproc.resampledata",
-         "timelockanalysis": ".statistics.timelockanalysis", "spike_psth": ".statistics.spike_psth"}
+         "timelockanalysis": ".statistics.timelockanalysis", "spike_psth": ".statistics.spike_psth",
+         "selectdata": ".datatype.selectdata", "copy": ".datatype.selectdata", "redefinetrial": ".datatype.redefinetrial"}
 
 
 def release_device_buffers():

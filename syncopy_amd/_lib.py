@@ -125,6 +125,8 @@ SIGNATURES = {
     "spyhip_arith": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, c_i64p, c_i64p,
                                C.c_double, C.c_double, c_i64p, vp, C.c_int64, C.c_int64, c_i32p, vp, C.c_int64, C.c_int64,
                                vp, C.c_int64]),
+    "spyhip_select": (C.c_int, [vp, C.c_int, vp, C.c_int64, c_i64p, c_i32p, c_i64p, c_i64p, c_i32p, vp, c_i64p, vp,
+                                C.c_int64, vp, C.c_int64]),
 }
 
 

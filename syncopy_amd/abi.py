@@ -372,6 +372,42 @@ class Device:
             for b in bufs:
                 b.free()
 
+    # ---- data selection
+    def select(self, data, trials, axes=None):
+        """The trials of `data` (rows x up to three inner axes; elements of 4, 8 or 16 bytes), stacked: `trials` (T, 2)
+        are [start, stop) rows, in any order, repeated or empty; `axes`: per inner axis None (all of it), (start, count)
+        or an array of indices.  What `np.concatenate([data[a:b][np.ix_(...)] ...])` gives, bit for bit.  See
+        spyhip_select in include/spyhip.h."""
+        from .datatype.selectdata import select_axes
+        data = np.ascontiguousarray(data)
+        trl = np.asarray(trials, dtype=np.int64).reshape(-1, 2)
+        n = trl[:, 1] - trl[:, 0]
+        if data.ndim < 1 or data.ndim > 4 or np.any(n < 0) or np.any(trl[:, 0] < 0) or np.any(trl[:, 1] > data.shape[0]):
+            raise ValueError("data must have 1 to 4 dimensions and hold the rows of every trial")
+        extent, kind, start, count, idx = select_axes(data.shape[1:], axes)
+        starts = np.concatenate(([0], np.cumsum(n))).astype(np.int64)
+        desc = np.ascontiguousarray(np.stack([starts[:-1], trl[:, 0], n], axis=1))
+        shape = (int(starts[-1]),) + tuple(int(c) for c in count[4 - data.ndim:])
+        if int(np.prod(shape)) == 0:
+            return np.empty(shape, dtype=data.dtype)
+        bufs = []
+        try:
+            src_d, out = self._put(data, data.dtype), Buffer(self, shape, data.dtype)
+            bufs += [src_d, out]
+            desc_d, idx_d = self._put(desc, np.int64), None if idx is None else self._put(idx, np.int32)
+            bufs += [desc_d] + ([] if idx_d is None else [idx_d])
+            check(self.lib.spyhip_select(self.handle, data.dtype.itemsize, src_d.ptr, data.shape[0],
+                                         extent.ctypes.data_as(_lib.c_i64p), kind.ctypes.data_as(_lib.c_i32p),
+                                         start.ctypes.data_as(_lib.c_i64p), count.ctypes.data_as(_lib.c_i64p),
+                                         None if idx is None else idx.ctypes.data_as(_lib.c_i32p),
+                                         None if idx_d is None else idx_d.ptr, desc.ctypes.data_as(_lib.c_i64p), desc_d.ptr,
+                                         desc.shape[0], out.ptr, shape[0]), "spyhip_select")
+            return out.numpy()
+        finally:
+            self.synchronize()
+            for b in bufs:
+                b.free()
+
     def close(self):
         if self.handle is not None:
             self.lib.spyhip_ctx_destroy(self.handle)

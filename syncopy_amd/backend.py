@@ -1500,3 +1500,31 @@ def arith(op, a, desc, out, scalar=0.0, array=None, operand=None, chan=None):
                                None if chan_h is None else chan_h.ctypes.data_as(_lib.c_i32p), _ptr(chan_d),
                                int(out.shape[-1]), int(a.shape[-1]), _ptr(out), int(out.shape[0])), "spyhip_arith")
     return out
+
+
+# ---- data selection (csrc/select.hip) ----------------------------------------------------------------------------------
+from .datatype.selectdata import select_axes  # noqa: E402  (NumPy only: abi.py shares it)
+
+
+def select(src, desc, out, axes=None):
+    """out = the rows of `src` that `desc` names ((ntrials, 3) int64 on the host: output row, source row, rows; see
+    include/spyhip.h: spyhip_select), of every row the elements that `axes` selects, one launch.  src, out: tensors of one
+    dtype whose first axis are the rows; src may be a view into a larger allocation as long as it is contiguous.  axes: per
+    inner axis of src None (all of it), (start, count) or an array of indices."""
+    assert src.is_cuda and out.is_cuda and src.is_contiguous() and out.is_contiguous() and 1 <= src.dim() == out.dim() <= 4
+    assert src.dtype == out.dtype
+    desc = np.ascontiguousarray(desc, dtype=np.int64).reshape(-1, 3)
+    if desc.shape[0] == 0 or out.numel() == 0:
+        return out
+    extent, kind, start, count, idx = select_axes(tuple(src.shape[1:]), axes)
+    assert tuple(out.shape[1:]) == tuple(int(c) for c in count[4 - src.dim():])
+    idx_d = None if idx is None else torch.from_numpy(idx).to(src.device)
+    desc_d = torch.from_numpy(desc).to(src.device)
+    ctx = _stat_ctx(src)
+    check(ctx.lib.spyhip_select(ctx.handle, src.element_size(), _ptr(src), int(src.shape[0]),
+                                extent.ctypes.data_as(_lib.c_i64p), kind.ctypes.data_as(_lib.c_i32p),
+                                start.ctypes.data_as(_lib.c_i64p), count.ctypes.data_as(_lib.c_i64p),
+                                None if idx is None else idx.ctypes.data_as(_lib.c_i32p), _ptr(idx_d),
+                                desc.ctypes.data_as(_lib.c_i64p), _ptr(desc_d), desc.shape[0], _ptr(out), int(out.shape[0])),
+          "spyhip_select")
+    return out
