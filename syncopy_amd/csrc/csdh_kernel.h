@@ -19,9 +19,20 @@
 //     outputs.  The minus sign costs no operand negation: the Im accumulator changes sign once per chunk between the
 //     two product groups (Ai Br first, negate, Ar Bi; the next chunk finds the planes swapped by the loader and so runs
 //     the same instructions as Ar Bi first, negate, Ai Br), and the epilogue takes the parity of the chunk count out.
+//   * the 16 DIAGONAL sub-tiles (row block = column block) repeat nothing Hermitian symmetry provides: with the fp16
+//     planes Rh, Rl, Ih, Il of the block (rows x 16 each) the 12 products are Re = Rh'Rh + Rh'Rl + Rl'Rh + Ih'Ih + Ih'Il
+//     + Il'Ih and Im = I'R - R'I, but Rl'Rh = (Rh'Rl)' and R'I = (I'R)'.  Such a tile accumulates
+//         S = Rh'Rh + Ih'Ih (2 instructions),  P = Rh'Rl + Ih'Il (2),  M = Ih'Rh + Ih'Rl + Il'Rh (3)
+//     - 7 instructions instead of 12, one operand block instead of two - and the epilogue forms Re = S + P + P' and
+//     Im = M - M' ONCE (csdh_fold_diagonal: transposes of the 16 x 16 float32 tiles through the LDS the loop has left).
+//     S and P do not notice the loader's plane swap; M does (an odd chunk adds R'I = the transpose of what an even one
+//     adds), so it changes sign once per chunk like every other Im accumulator: then M - M' is the chunks' sum of
+//     (I'R - R'I) up to the same parity of the chunk count.  Re of such a block is symmetric, Im antisymmetric with a
+//     zero diagonal, bit for bit.  Per chunk and workgroup: 120 x 12 + 16 x 7 = 1552 matrix instructions (1632 without).
 //
 // Work decomposition: one 512-thread workgroup per frequency, the 136 lower-triangle sub-tiles dealt to the 8 waves by
-// M3Tab<256> (csd3m_kernel.h), 2 x 17 accumulators of 4 registers per wave.  A chunk = 32 rows of X[., f, :]
+// HTab (below: 15 off-diagonal + 2 diagonal sub-tiles per wave = 194 matrix instructions per wave and chunk, the same
+// for all), 2 x 17 + 2 accumulators of 4 registers per wave.  A chunk = 32 rows of X[., f, :]
 // (64 KiB of spectra): wave w fetches rows 8 (w / 2) ... + 7 of channels 128 (w % 2) + 64 phase + lane (8-byte loads,
 // 512 contiguous bytes per wave instruction), splits, and writes one 16-byte unit = 8 rows of one channel of one
 // plane per ds_write_b128 into the layout the fragments are read in:
@@ -83,26 +94,99 @@ constexpr int CSDH_BUF = 4 * CSDH_PLANE;              // 32 rows of 256 complex 
 constexpr int CSDH_LDS_BYTES = 2 * CSDH_BUF + 1024 + 16;   // + the channels' scale exponents + the validity word
 constexpr int CSDH_KROWS = 32;
 
+// ---- the deal: which 17 of the 136 lower-triangle sub-tiles (row block, column block; 16 channels each) a wave owns.
+// M3Tab<256> (the float32 kernel's deal) leaves all 16 diagonal sub-tiles to waves 6 and 7; here a diagonal sub-tile
+// is 7 matrix instructions against 12, so every wave gets two of them and 15 others:
+//   g 0-5: the 4 x 4 squares rows 8-11 x columns 0-3, 8-11 x 4-7, 12-15 x 0-3, 12-15 x 4-7, 4-7 x 0-3, 12-15 x 8-11,
+//          each without its corner (first row, last column), + two diagonal blocks that are among the square's column
+//          blocks (g 0, 2, 5: they sit in a B slot when their turn comes) or its last two row blocks (g 1, 3, 4: A slot)
+//   g 6:   below the diagonal of blocks {0-3} and of {4-7}, the corners of g 0, 2, 4, diagonal blocks 4, 5
+//   g 7:   below the diagonal of blocks {8-11} and of {12-15}, the corners of g 1, 3, 5, diagonal blocks 12, 13
+template <int NT_ = 17>
+struct HTabT {
+    static constexpr int NT = NT_, ND = 2;      // sub-tiles / diagonal sub-tiles per wave
+    struct Gen { int ta[8][NT], tb[8][NT]; };
+    static constexpr Gen make() {
+        constexpr int SQR[6] = {8, 8, 12, 12, 4, 12}, SQC[6] = {0, 4, 0, 4, 0, 8};
+        constexpr int DG[8] = {0, 10, 2, 14, 6, 8, 4, 12};       // wave g: diagonal blocks DG[g], DG[g] + 1
+        Gen g{};
+        int n[8] = {};
+        for (int w = 0; w < 6; ++w)
+            for (int r = SQR[w]; r < SQR[w] + 4; ++r)
+                for (int c = SQC[w]; c < SQC[w] + 4; ++c) {
+                    const int o = (r == SQR[w] && c == SQC[w] + 3) ? 6 + (w & 1) : w;      // the corner goes to wave 6 / 7
+                    g.ta[o][n[o]] = r; g.tb[o][n[o]] = c; ++n[o];
+                }
+        for (int w = 6; w < 8; ++w)
+            for (int b = 8 * (w - 6); b < 8 * (w - 6) + 8; b += 4)
+                for (int r = b; r < b + 4; ++r)
+                    for (int c = b; c < r; ++c) { g.ta[w][n[w]] = r; g.tb[w][n[w]] = c; ++n[w]; }
+        for (int w = 0; w < 8; ++w)
+            for (int d = DG[w]; d < DG[w] + 2; ++d) { g.ta[w][n[w]] = d; g.tb[w][n[w]] = d; ++n[w]; }
+        return g;
+    }
+    static constexpr Gen T = make();
+    static constexpr int ta(int g, int t) { return T.ta[g][t]; }       // row block (0..15) of sub-tile t of wave g
+    static constexpr int tb(int g, int t) { return T.tb[g][t]; }       // column block
+    static constexpr bool diag(int g, int t) { return T.ta[g][t] == T.tb[g][t]; }
+    static constexpr int didx(int g, int t) {                          // a diagonal sub-tile's place among the wave's
+        int d = 0;
+        for (int u = 0; u < t; ++u) d += diag(g, u) ? 1 : 0;
+        return d;
+    }
+    // every sub-tile on or below the diagonal exactly once, ND diagonal ones per wave
+    static constexpr bool complete() {
+        int seen[16][16] = {};
+        for (int w = 0; w < 8; ++w) {
+            int nd = 0;
+            for (int t = 0; t < NT; ++t) {
+                if (T.ta[w][t] < T.tb[w][t] || T.ta[w][t] > 15 || T.tb[w][t] < 0) return false;
+                ++seen[T.ta[w][t]][T.tb[w][t]];
+                nd += diag(w, t) ? 1 : 0;
+            }
+            if (nd != ND) return false;
+        }
+        for (int r = 0; r < 16; ++r)
+            for (int c = 0; c <= r; ++c)
+                if (seen[r][c] != 1) return false;
+        return true;
+    }
+};
+using HTab = HTabT<>;       // (a template so that its table is built where it is first used: after the class is complete)
+static_assert(HTab::complete(), "the deal of K4h's sub-tiles");
+static_assert(HTab::NT == M3Tab<256>::NT, "17 sub-tiles per wave in either deal");
+
 // ---- per-wave schedule: the order of the wave's sub-tiles and which fragment slot every operand block sits in.
 // Two A slots (ping-pong: the next row block lands while the current one is multiplied), two B slots; a diagonal
-// sub-tile reads its column operand from the A slot.  Sub-tiles are walked column pair by column pair so that a 4 x 4
+// sub-tile has ONE operand block: it is looked for (and fetched) among the B slots if the wave otherwise uses the block
+// as a column block only, among the A slots if not.  Sub-tiles are walked column pair by column pair so that a 4 x 4
 // square loads each column block once and each row block twice.
 template <int G>
 struct HPlan {
-    using TAB = M3Tab<256>;
+    using TAB = HTab;
     static constexpr int NT = TAB::NT;
     struct P {
         int tile[NT];       // walk order -> index into TAB::ta / tb
         int ablk[NT], bblk[NT];      // block indices (0..15) of the operands
-        int aslot[NT], bslot[NT];    // bslot 2 = the A slot (diagonal)
+        int aslot[NT], bslot[NT];
         bool aload[NT], bload[NT];   // the operand is fetched for this step (else it is still in its slot)
+        bool diag[NT], dinb[NT];     // diagonal sub-tile; ... whose one operand is B[bslot] (else A[aslot])
     };
+    static constexpr bool column_only(int x) {       // block x: a column block, never a row block, of the other sub-tiles
+        bool col = false;
+        for (int t = 0; t < NT; ++t) {
+            if (TAB::diag(G, t)) continue;
+            if (TAB::ta(G, t) == x) return false;
+            col = col || TAB::tb(G, t) == x;
+        }
+        return col;
+    }
     static constexpr P make() {
         P p{};
         int key[NT] = {};
         for (int t = 0; t < NT; ++t) {
             p.tile[t] = t;
-            key[t] = (TAB::tb(G, t) >> 1) * 64 + TAB::ta(G, t) * 8 + TAB::tb(G, t);
+            key[t] = (TAB::tb(G, t) >> 1) * 256 + TAB::ta(G, t) * 16 + TAB::tb(G, t);
         }
         for (int i = 1; i < NT; ++i)            // insertion sort by (column pair, row block, column block)
             for (int j = i; j > 0 && key[j] < key[j - 1]; --j) {
@@ -113,17 +197,22 @@ struct HPlan {
         int alast = 1, blast = 1;               // slot used by the previous step (the other one is the victim)
         for (int s = 0; s < NT; ++s) {
             const int t = p.tile[s];
-            const int x = TAB::blk(G, TAB::ta(G, t)), y = TAB::blk(G, TAB::tb(G, t));
+            const int x = TAB::ta(G, t), y = TAB::tb(G, t);
             p.ablk[s] = x;
             p.bblk[s] = y;
-            if (ac[0] == x) { p.aslot[s] = 0; p.aload[s] = false; }
-            else if (ac[1] == x) { p.aslot[s] = 1; p.aload[s] = false; }
-            else { p.aslot[s] = 1 - alast; p.aload[s] = true; ac[1 - alast] = x; }
-            alast = p.aslot[s];
-            if (x == y) { p.bslot[s] = 2; p.bload[s] = false; }
-            else {
-                if (bc[0] == y) { p.bslot[s] = 0; p.bload[s] = false; }
-                else if (bc[1] == y) { p.bslot[s] = 1; p.bload[s] = false; }
+            p.diag[s] = x == y;
+            p.dinb[s] = x == y && column_only(x);
+            p.aslot[s] = alast; p.aload[s] = false;
+            p.bslot[s] = blast; p.bload[s] = false;
+            if (!p.dinb[s]) {
+                if (ac[0] == x) { p.aslot[s] = 0; }
+                else if (ac[1] == x) { p.aslot[s] = 1; }
+                else { p.aslot[s] = 1 - alast; p.aload[s] = true; ac[1 - alast] = x; }
+                alast = p.aslot[s];
+            }
+            if (!p.diag[s] || p.dinb[s]) {
+                if (bc[0] == y) { p.bslot[s] = 0; }
+                else if (bc[1] == y) { p.bslot[s] = 1; }
                 else { p.bslot[s] = 1 - blast; p.bload[s] = true; bc[1 - blast] = y; }
                 blast = p.bslot[s];
             }
@@ -161,30 +250,99 @@ __device__ __forceinline__ void csdh_tile(const f16x8 (&X)[4], const f16x8 (&Y)[
     __builtin_amdgcn_s_setprio(0);
 }
 
+// One DIAGONAL sub-tile, 32 rows: X = the fragments of its one block.  S += P0h'P0h + P1h'P1h, P += P0h'P0l + P1h'P1l (the
+// same whichever of the planes is the real part); M += P1'P0 without the lo lo' term, then M changes sign like `im`
+// above: even chunks add Ih'R.. = I'R, odd ones R'I = its transpose to the negated sum, so that M - M' (the epilogue's)
+// is the sum over the chunks of I'R - R'I up to the sign (-1)^chunks.
+__device__ __forceinline__ void csdh_diag_tile(const f16x8 (&X)[4], f32x4& s, f32x4& p, f32x4& m) {
+    __builtin_amdgcn_s_setprio(1);
+    m = __builtin_amdgcn_mfma_f32_16x16x32_f16(X[2], X[0], m, 0, 0, 0);
+    m = __builtin_amdgcn_mfma_f32_16x16x32_f16(X[2], X[1], m, 0, 0, 0);
+    m = __builtin_amdgcn_mfma_f32_16x16x32_f16(X[3], X[0], m, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_16x16x32_f16(X[0], X[0], s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_16x16x32_f16(X[2], X[2], s, 0, 0, 0);
+    p = __builtin_amdgcn_mfma_f32_16x16x32_f16(X[0], X[1], p, 0, 0, 0);
+    p = __builtin_amdgcn_mfma_f32_16x16x32_f16(X[2], X[3], p, 0, 0, 0);
+    if (!(CSDH_ABL & 32)) m = -m;
+    __builtin_amdgcn_s_setprio(0);
+}
+
+// Step s of wave G's walk on the fragment slots A, B: re / im = the accumulators of the wave's 17 sub-tiles (a diagonal
+// one keeps S in re and M in im), pd = P of its diagonal sub-tiles.
+template <int G, int s>
+__device__ __forceinline__ void csdh_step(const f16x8 (&A)[2][4], const f16x8 (&B)[2][4], f32x4 (&re)[HTab::NT], f32x4 (&im)[HTab::NT],
+                                          f32x4 (&pd)[HTab::ND]) {
+    using PL = HPlan<G>;
+    constexpr int t = PL::T.tile[s];
+    if constexpr (PL::T.diag[s]) {
+        const f16x8(&X)[4] = PL::T.dinb[s] ? B[PL::T.bslot[s]] : A[PL::T.aslot[s]];
+        csdh_diag_tile(X, re[t], pd[HTab::didx(G, t)], im[t]);
+    } else {
+        csdh_tile(A[PL::T.aslot[s]], B[PL::T.bslot[s]], re[t], im[t]);
+    }
+}
+
+// After the last chunk (and the barrier behind it: the operand buffers are free), for the diagonal sub-tiles of wave G:
+// re <- S + P + P', im <- M - M'.  The transposes go through `ts`, 16 x 17 floats of LDS that belong to this wave.  Lane
+// l holds column l & 15 and rows 4 (l >> 4) + r of a tile.  (S + S') / 2 is S wherever the matrix core gave S[i][j] and
+// S[j][i] the same bits, and symmetric by construction in any case.
+template <int G>
+__device__ __forceinline__ void csdh_fold_diagonal(f32x4 (&re)[HTab::NT], f32x4 (&im)[HTab::NT], f32x4 (&pd)[HTab::ND], float* ts,
+                                                   int lane) {
+    const int l15 = lane & 15, lq = lane >> 4;
+    auto transposed = [&](const f32x4& v) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ts[(4 * lq + r) * 17 + l15] = v[r];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        f32x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = ts[l15 * 17 + 4 * lq + r];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // read before the next tile overwrites it
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        return o;
+    };
+    m3_for<0, HTab::NT>([&](auto tc) {
+        constexpr int t = decltype(tc)::value;
+        if constexpr (HTab::diag(G, t)) {
+            constexpr int d = HTab::didx(G, t);
+            const f32x4 st = transposed(re[t]), pt = transposed(pd[d]), mt = transposed(im[t]);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                re[t][r] = 0.5f * (re[t][r] + st[r]) + (pd[d][r] + pt[r]);
+                im[t][r] = im[t][r] - mt[r];
+            }
+        }
+    });
+}
+
 // After the last chunk: validity of the frequency, then acc += sub-tile / (2^k_i 2^k_j).  `kexp(channel)` = the scale
-// exponent the operands were split with.
+// exponent the operands were split with; `ts`: see csdh_fold_diagonal.
 template <int G, class KEXP>
-__device__ __forceinline__ void csdh_finish(const CsdhArgs& a, f32x4 (&re)[M3Tab<256>::NT], f32x4 (&im)[M3Tab<256>::NT], int nchunk,
-                                            int f, int lane, int* vword, KEXP kexp) {
-    using TAB = M3Tab<256>;
+__device__ __forceinline__ void csdh_finish(const CsdhArgs& a, f32x4 (&re)[HTab::NT], f32x4 (&im)[HTab::NT], f32x4 (&pd)[HTab::ND],
+                                            float* ts, int nchunk, int f, int lane, int* vword, KEXP kexp) {
+    using TAB = HTab;
     constexpr int NT = TAB::NT;
     const int l15 = lane & 15, lq = lane >> 4;
     const long long nrows = a.nrows;
+    csdh_fold_diagonal<G>(re, im, pd, ts, lane);       // from here on a diagonal sub-tile holds Re and Im like any other
     // ---- the Im accumulators carry the sign (-1)^nchunk relative to (even chunks) Im = Ai Br - Ar Bi ... :
     // even chunk: planes (re, im): first group = Ai Br (+), then negated, + Ar Bi  ->  -(I + Ai Br - Ar Bi)
     // odd chunk:  planes (im, re): first group = Ar Bi added to -(I...), negated -> I... - Ar Bi, + Ai Br
     const float isign = (nchunk & 1) ? -1.f : 1.f;
 
-    // ---- validity of the frequency: the diagonal of the scaled accumulation (waves 6 and 7 own the diagonal sub-tiles)
+    // ---- validity of the frequency: the diagonal of the scaled accumulation (every wave owns two diagonal sub-tiles)
     {
         const float floor2 = (float)nrows * 0.015625f;            // rms^2 >= 2^-6 in scaled units
         bool bad = false;
         m3_for<0, NT>([&](auto tc) {
             constexpr int t = decltype(tc)::value;
-            if constexpr (TAB::blk(G, TAB::ta(G, t)) == TAB::blk(G, TAB::tb(G, t))) {
+            if constexpr (TAB::diag(G, t)) {
                 // an all-zero diagonal entry is only innocent for a channel that IS zero (a scale of 2^-114 for an
                 // Inf "maximum" would flush a whole channel to zero otherwise)
-                const bool dead = a.absmax[TAB::blk(G, TAB::ta(G, t)) * 16 + l15] == 0.f;
+                const bool dead = a.absmax[TAB::ta(G, t) * 16 + l15] == 0.f;
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (4 * lq + r == l15) {
@@ -203,7 +361,7 @@ __device__ __forceinline__ void csdh_finish(const CsdhArgs& a, f32x4 (&re)[M3Tab
     // ---- acc += sub-tile / (2^k_i 2^k_j).  Lane l holds column (l & 15) and rows 4 (l >> 4) + r of the 16 x 16 block.
     m3_for<0, NT>([&](auto tc) {
         constexpr int t = decltype(tc)::value;
-        constexpr int bi = TAB::blk(G, TAB::ta(G, t)), bj = TAB::blk(G, TAB::tb(G, t));
+        constexpr int bi = TAB::ta(G, t), bj = TAB::tb(G, t);
         static_assert(bi >= bj, "a sub-tile lies on or below the diagonal");
         float2* const pb = a.acc + (size_t)f * 65536 + (size_t)(bi * 16 + 4 * lq) * 256 + bj * 16 + l15;
         const int kj = kexp(bj * 16 + l15);
@@ -220,9 +378,9 @@ __device__ __forceinline__ void csdh_finish(const CsdhArgs& a, f32x4 (&re)[M3Tab
 
 template <int G>
 __device__ __forceinline__ void csdh_wave(const CsdhArgs& a, char* lds, int f, int lane) {
-    using TAB = M3Tab<256>;
+    using TAB = HTab;
     using PL = HPlan<G>;
-    constexpr int NT = TAB::NT;
+    constexpr int NT = TAB::NT, ND = TAB::ND;
     constexpr int KG = G >> 1, CHH = G & 1;          // this wave converts rows 8 KG ... of channels 128 CHH ...
     const int l15 = lane & 15, lq = lane >> 4;
     int* const kexp = reinterpret_cast<int*>(lds + 2 * CSDH_BUF);          // [256] scale exponents
@@ -259,7 +417,16 @@ __device__ __forceinline__ void csdh_wave(const CsdhArgs& a, char* lds, int f, i
             for (int i = 0; i < 8; ++i) {
                 if (CSDH_ABL & 1) st[i] = f32x2{(float)(i + lane), (float)(c - lane)};
                 else if ((CSDH_ABL & 128) && c > 2) asm volatile("" : "+v"(st[i]));      // keep the (real) values of chunk 2
-                else st[i] = *reinterpret_cast<const f32x2*>(nextp + i * rowbytes + 512 * ph + voff);
+                else {
+                    // the row's address stays a scalar pair (global_load with an SGPR base and the lane's 32-bit offset):
+                    // left alone, the compiler folds i * rowbytes + voff into eight 64-bit VECTOR offsets that live
+                    // across the whole loop - registers the accumulators need
+                    typedef const __attribute__((address_space(1))) char gchar;          // (global memory, said out loud:
+                    typedef const __attribute__((address_space(1))) f32x2 gf32x2;       // behind the asm nothing infers it)
+                    gchar* rowp = (gchar*)(nextp + i * rowbytes);
+                    asm("" : "+s"(rowp));
+                    st[i] = *(gf32x2*)(rowp + voff + 512 * ph);
+                }
             }
         } else {
             const int r0 = c * CSDH_KROWS + 8 * KG;
@@ -326,11 +493,15 @@ __device__ __forceinline__ void csdh_wave(const CsdhArgs& a, char* lds, int f, i
         *reinterpret_cast<u32x4*>(wi + CSDH_PLANE) = il;
     };
 
-    f32x4 re[NT], im[NT];
+    f32x4 re[NT], im[NT], pd[ND];                // (a diagonal sub-tile: S in re, M in im, P in pd)
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) { re[t][r] = 0.f; im[t][r] = 0.f; }
+#pragma unroll
+    for (int d = 0; d < ND; ++d)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pd[d][r] = 0.f;
 
     nextp -= (size_t)CSDH_KROWS * rowbytes;      // chunk 0
     fetch(0, 0);
@@ -359,21 +530,18 @@ __device__ __forceinline__ void csdh_wave(const CsdhArgs& a, char* lds, int f, i
 
     for (int c = 0; c < nchunk; ++c) {
         CSDH_STAMP(0);
-        ldfrag(A[PL::T.aslot[0]], PL::T.ablk[0]);
-        if constexpr (PL::T.bload[0]) ldfrag(B[PL::T.bslot[0] & 1], PL::T.bblk[0]);
+        if constexpr (PL::T.aload[0]) ldfrag(A[PL::T.aslot[0]], PL::T.ablk[0]);
+        if constexpr (PL::T.bload[0]) ldfrag(B[PL::T.bslot[0]], PL::T.bblk[0]);
         fetch(c + 1, 0);          // (the last iteration converts rows that do not exist into the idle buffer: zeros)
         __builtin_amdgcn_sched_barrier(CSDH_FENCE);      // the loads are issued HERE, ahead of the chunk's matrix work
         m3_for<0, NT>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
-            constexpr int t = PL::T.tile[s];
             // operands of the next step land while this one multiplies
             if constexpr (s + 1 < NT) {
                 if constexpr (PL::T.aload[s + 1]) ldfrag(A[PL::T.aslot[s + 1]], PL::T.ablk[s + 1]);
                 if constexpr (PL::T.bload[s + 1]) ldfrag(B[PL::T.bslot[s + 1]], PL::T.bblk[s + 1]);
             }
-            const f16x8(&X)[4] = A[PL::T.aslot[s]];
-            const f16x8(&Y)[4] = PL::T.bslot[s] == 2 ? A[PL::T.aslot[s]] : B[PL::T.bslot[s] & 1];
-            csdh_tile(X, Y, re[t], im[t]);
+            csdh_step<G, s>(A, B, re, im, pd);
             if constexpr (s == S1) {
                 CSDH_STAMP(2);
 #ifdef CSDH_STAMPS
@@ -402,7 +570,9 @@ __device__ __forceinline__ void csdh_wave(const CsdhArgs& a, char* lds, int f, i
         nextp += (size_t)CSDH_KROWS * rowbytes;
     }
 
-    csdh_finish<G>(a, re, im, nchunk, f, lane, vword, [&](int ch) { return kexp[ch]; });
+    // (behind the loop's last barrier nobody reads or writes the operand buffers any more: 2 KiB of them per wave for
+    // the epilogue's transposes)
+    csdh_finish<G>(a, re, im, pd, reinterpret_cast<float*>(lds + G * 2048), nchunk, f, lane, vword, [&](int ch) { return kexp[ch]; });
 }
 
 template <int G0, int G1>

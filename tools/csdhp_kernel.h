@@ -37,9 +37,9 @@ __host__ __device__ constexpr int csdhp_row_base(int r) { return r * CSDHP_ROW +
 
 template <int G>
 __device__ __forceinline__ void csdhp_wave(const CsdhArgs& a, char* lds, int f, int lane) {
-    using TAB = M3Tab<256>;
+    using TAB = HTab;
     using PL = HPlan<G>;
-    constexpr int NT = TAB::NT;
+    constexpr int NT = TAB::NT, ND = TAB::ND;
     int* const vword = reinterpret_cast<int*>(lds + 2 * CSDHP_BUF);
     if (G == 0 && lane == 0) *vword = 1;
 
@@ -65,11 +65,15 @@ __device__ __forceinline__ void csdhp_wave(const CsdhArgs& a, char* lds, int f, 
         }
     };
 
-    f32x4 re[NT], im[NT];
+    f32x4 re[NT], im[NT], pd[ND];
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) { re[t][r] = 0.f; im[t][r] = 0.f; }
+#pragma unroll
+    for (int d = 0; d < ND; ++d)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pd[d][r] = 0.f;
 
     stage(0);
     spy_wait_vmem();
@@ -101,20 +105,17 @@ __device__ __forceinline__ void csdhp_wave(const CsdhArgs& a, char* lds, int f, 
     };
 
     for (int c = 0; c < nchunk; ++c) {
-        ldfrag(A[PL::T.aslot[0]], PL::T.ablk[0]);
-        if constexpr (PL::T.bload[0]) ldfrag(B[PL::T.bslot[0] & 1], PL::T.bblk[0]);
+        if constexpr (PL::T.aload[0]) ldfrag(A[PL::T.aslot[0]], PL::T.ablk[0]);
+        if constexpr (PL::T.bload[0]) ldfrag(B[PL::T.bslot[0]], PL::T.bblk[0]);
         if (c + 1 < nchunk) stage(c + 1);
         __builtin_amdgcn_sched_barrier(0);                   // the copies are issued HERE, ahead of the chunk's matrix work
         m3_for<0, NT>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
-            constexpr int t = PL::T.tile[s];
             if constexpr (s + 1 < NT) {
                 if constexpr (PL::T.aload[s + 1]) ldfrag(A[PL::T.aslot[s + 1]], PL::T.ablk[s + 1]);
                 if constexpr (PL::T.bload[s + 1]) ldfrag(B[PL::T.bslot[s + 1]], PL::T.bblk[s + 1]);
             }
-            const f16x8(&X)[4] = A[PL::T.aslot[s]];
-            const f16x8(&Y)[4] = PL::T.bslot[s] == 2 ? A[PL::T.aslot[s]] : B[PL::T.bslot[s] & 1];
-            csdh_tile(X, Y, re[t], im[t]);
+            csdh_step<G, s>(A, B, re, im, pd);
         });
         spy_wait_vmem();                                     // this wave's rows of chunk c + 1 have landed
         __syncthreads();
@@ -124,7 +125,8 @@ __device__ __forceinline__ void csdhp_wave(const CsdhArgs& a, char* lds, int f, 
         a1 = lanebase + odd * CSDHP_BUF + 16 * (1 - odd);
     }
 
-    csdh_finish<G>(a, re, im, nchunk, f, lane, vword, [&](int ch) { return csdh_exponent(a.absmax[ch]); });
+    csdh_finish<G>(a, re, im, pd, reinterpret_cast<float*>(lds + G * 2048), nchunk, f, lane, vword,
+                   [&](int ch) { return csdh_exponent(a.absmax[ch]); });
 }
 
 template <int G0, int G1>

@@ -7,6 +7,8 @@ hipcc -O2 tools/pmc_harness.cpp -Iinclude -Lsyncopy_amd -lspyhip -Wl,-rpath,$PWD
 B=${1:-500}
 BLK=${2:-0}
 gpurun_out/pmc/harness $B 1 3 $BLK || exit 1
+O=$(dirname "$(ls */pmc/harness | head -1)")      # the output directory made above, where the harness was built
+# counters in runs of their own (no tracing alongside), each under a time limit; a group that fails ends the session
 i=0
 for grp in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE" \
            "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS" \
@@ -14,8 +16,10 @@ for grp in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES GRBM
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS" \
            "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
-  rocprofv3 --pmc $grp --kernel-trace -d gpurun_out/pmc/g$i -o p --output-format csv -- gpurun_out/pmc/harness $B 2 3 $BLK > gpurun_out/pmc/g$i.log 2>&1
-  echo "group $i ($grp): rc=$?"
+  timeout -k 10 300 rocprofv3 --pmc $grp -d $O/g$i -o p --output-format csv -- $O/harness $B 2 3 $BLK > $O/g$i.log 2>&1
+  rc=$?
+  echo "group $i ($grp): rc=$rc"
+  [ $rc -eq 0 ] || { tail -5 $O/g$i.log; exit 1; }
 done
 python - $B $BLK <<'PY'
 import csv, glob, collections
