@@ -65,8 +65,9 @@ int launch_tail(spyhip_ctx* ctx, CsdArgs a, const CsdStep& s) {
     int rc = launch_accum<1, 1>(ctx, a, s);
     if (rc) return rc;
     const long long n = (long long)nf * a.C * a.C;
-    hipLaunchKernelGGL(spycsd::csd_reduce_parts_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 4096)),
-                       dim3(256), 0, ctx->stream, a.acc, a.part, nsplit - 1, f0, nf, a.C);
+    const long long blocks = std::min<long long>((n + 255) / 256, ctx->limits.elementwise_blocks);
+    hipLaunchKernelGGL(spycsd::csd_reduce_parts_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a.acc, a.part,
+                       nsplit - 1, f0, nf, a.C);
     SPY_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -114,8 +115,8 @@ int run_route(spyhip_ctx* ctx, const spycsd::CsdRoute& r, const void* spec_d, vo
             case StepKind::M4_RECT: rc = spycsd::m4_launch_rect(ctx->stream, a, s.nprow); break;
             case StepKind::RANK1: {
                 const long long tot = (long long)nfreq * nchan * nchan;
-                hipLaunchKernelGGL(csd_rank1_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 65535)), dim3(256), 0,
-                                   ctx->stream, a.spec, nfreq, nchan, a.acc);
+                hipLaunchKernelGGL(csd_rank1_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, ctx->limits.workgroups)),
+                                   dim3(256), 0, ctx->stream, a.spec, nfreq, nchan, a.acc);
                 SPY_HIP_CHECK(hipGetLastError());
                 break;
             }
@@ -133,7 +134,8 @@ spycsd::CsdQuery make_query(const spyhip_ctx* ctx, int64_t nrows, int nfreq, int
     q.phase_exact = ctx->csd_phase_exact != 0;
     q.num_cu = ctx->num_cu;
     q.lds_per_block = ctx->lds_per_block;
-    return q;                       // (have_m3 stays null: csd3m_{a..h}.hip + csd3m_x.hip hold every width up to 512)
+    q.have_m3 = ctx->have_m3;       // (null in the library: csd3m_{a..h}.hip + csd3m_x.hip hold every width up to 512)
+    return q;
 }
 
 int csd_accumulate_impl(spyhip_ctx* ctx, const void* spec_d, int64_t nrows, int nfreq, int nchan, void* acc_d, int blocked) {
@@ -275,8 +277,7 @@ static int tril_move(spyhip_ctx* ctx, void* acc_d, int nfreq, int nchan, void* p
     if (!ctx || !acc_d || !packed_d) { spy::set_error("csd_tril: null argument"); return -1; }
     SPY_HIP_CHECK(hipSetDevice(ctx->device));
     const long long n = (long long)nfreq * nchan * nchan;
-    long long blocks = (n + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
+    const long long blocks = std::min<long long>((n + 255) / 256, 4 * ctx->limits.elementwise_blocks);
     if (unpack)
         hipLaunchKernelGGL(spycsd::csd_tril_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
                            reinterpret_cast<float2*>(acc_d), reinterpret_cast<float2*>(packed_d), nfreq, nchan);
@@ -301,8 +302,7 @@ extern "C" int spyhip_coh_normalize(spyhip_ctx* ctx, const void* csd_d, int nfre
     if (output < SPYHIP_OUT_POW || output > SPYHIP_OUT_ABSIMAG) { spy::set_error("coh_normalize: bad output %d", output); return -1; }
     SPY_HIP_CHECK(hipSetDevice(ctx->device));
     const long long n = (long long)nfreq * nchan * nchan;
-    long long blocks = (n + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
+    const long long blocks = std::min<long long>((n + 255) / 256, 2 * ctx->limits.elementwise_blocks);
     if (output == SPYHIP_OUT_FOURIER)
         hipLaunchKernelGGL(spycsd::coh_normalize_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
                            reinterpret_cast<const float2*>(csd_d), nfreq, nchan, output, out_d);

@@ -1,7 +1,7 @@
 // Which kernels serve a cross-spectral update (K4 / K4h), over which ranges and in which order: pure integer logic, no HIP
 // header and no runtime call, so that the launch policy is testable on any host (tests/test_csd_route.py) and shared by
-// the library (csd.hip walks the steps with hipLaunchKernelGGL) and the kernel emulator (tests/emu/emu_kernels.cpp walks
-// the same steps with emu::launch).
+// the library (csd.hip walks the steps with hipLaunchKernelGGL) and the kernel emulator (tests/emu/csd_emu.cpp compiles
+// csd.hip for the host, so the same walk runs there).
 #pragma once
 #include <cstddef>
 #include <cstdio>

@@ -18,8 +18,10 @@
 // (the CPU emulator of tests/emu lowers them so that the chunk loops and grid-stride loops run at test sizes).
 struct spyhip_limits {
     int64_t grid_yz = 65535;            // blocks along grid.y / grid.z
-    int64_t elementwise_blocks = 4096;  // workgroups of the grid-stride kernels of stats.hip
-    int64_t workgroups = 65535;         // workgroups of the median, variance and transposition launches
+    int64_t elementwise_blocks = 4096;  // workgroups of the grid-stride kernels of stats.hip and of the partial-sum reduction
+                                        // of csd.hip; its tril and coherence launches take 4 x and 2 x as many
+    int64_t workgroups = 65535;         // workgroups of the median, variance and transposition launches and of the rank-1
+                                        // cross-spectral update
     int64_t any64_chunk = INT64_MAX;    // work arrays of one float64 Hilbert launch, on top of spyhil::any64_chunk
 };
 
@@ -44,6 +46,7 @@ struct spyhip_ctx {
     int num_cu = 256;
     size_t lds_per_block = 160 * 1024;
     spyhip_limits limits;
+    bool (*have_m3)(int) = nullptr; // spycsd::CsdQuery::have_m3.  Like `limits`: nothing in the API sets it
 };
 
 namespace spy {

@@ -40,16 +40,21 @@ def build(force=False):
     return build_unit(os.path.join(HERE, "emu_kernels.cpp"), OUT, sources(), force=force)
 
 
+def build_library(name):
+    """tests/emu/<name>_emu.cpp: the library's own .hip files of one family on the runtime stand-in hip/hip_runtime.h"""
+    return build_unit(os.path.join(HERE, name + "_emu.cpp"), os.path.join(BUILD, f"lib{name}emu.so"), sources(), flags=("-I" + HERE,))
+
+
 def emulated_library(name):
-    """tests/emu/<name>_emu.cpp: the library's own .hip files of one family on the runtime stand-in hip/hip_runtime.h.
-    Its spyhip_* functions take the types of the public ABI (syncopy_amd._lib.SIGNATURES, plain data)."""
+    """build_library(name), loaded.  Its spyhip_* functions take the types of the public ABI (syncopy_amd._lib.SIGNATURES,
+    plain data)."""
     from syncopy_amd._lib import SIGNATURES
-    lib = C.CDLL(build_unit(os.path.join(HERE, name + "_emu.cpp"), os.path.join(BUILD, f"lib{name}emu.so"), sources(),
-                            flags=("-I" + HERE,)))
+    lib = C.CDLL(build_library(name))
     for fn, (res, args) in SIGNATURES.items():
         if hasattr(lib, fn):
             getattr(lib, fn).restype, getattr(lib, fn).argtypes = res, args
     lib.emu_ctx.restype, lib.emu_ctx.argtypes = C.c_void_p, [C.c_longlong] * 4
+    lib.emu_ctx_set_chip.restype, lib.emu_ctx_set_chip.argtypes = None, [C.c_void_p, C.c_int, C.c_longlong]
     lib.emu_ctx_scratch.restype, lib.emu_ctx_scratch.argtypes = C.c_void_p, [C.c_void_p]
     lib.emu_ctx_destroy.restype, lib.emu_ctx_destroy.argtypes = None, [C.c_void_p]
     lib.emu_launch_log.restype, lib.emu_launch_log.argtypes = C.c_longlong, [C.c_void_p, C.c_longlong]

@@ -147,115 +147,6 @@ def seq_mean(data, seg_start, seg_lo, seg_hi, nsig, chan_idx=None):
     return means
 
 
-def set_blocked(on):
-    """Channel-blocked hand-over layout for the following fft_exec / csd_accumulate calls."""
-    lib().emu_set_blocked(C.c_int(int(bool(on))))
-
-
-def csd_accumulate(spec, acc, force_tpw=0, blocked=False, force_4m=False, num_cu=None):
-    """Emulated spyhip_csd_accumulate: spec (R, F, C) complex64 - or (R, ceil(C/4), F, 4) with blocked=True -,
-    acc (F, C, C) complex64 (in place).  `force_4m`: 256 channels on the 4-multiplication kernel (SPYHIP_CSD_4M).
-    `num_cu`: compute units the route plans for (emulator only; None: so many that no launch is re-cut into a tail).
-    Returns a code for the kernel that ran (8 = the 3-multiplication kernel)."""
-    if num_cu is not None:
-        lib().emu_set_num_cu(C.c_longlong(num_cu))
-        try:
-            return csd_accumulate(spec, acc, force_tpw, blocked, force_4m)
-        finally:
-            lib().emu_set_num_cu(C.c_longlong(0))
-    if force_4m:
-        lib().emu_set_force_4m(1)
-        try:
-            return csd_accumulate(spec, acc, force_tpw, blocked)
-        finally:
-            lib().emu_set_force_4m(0)
-    spec = np.ascontiguousarray(spec, dtype=np.complex64)
-    assert acc.dtype == np.complex64 and acc.flags.c_contiguous
-    if blocked:
-        R, F, Cn = spec.shape[0], acc.shape[0], acc.shape[1]
-        assert spec.shape == (R, (Cn + 3) // 4, F, 4)
-        set_blocked(True)
-        try:
-            return lib().emu_csd_accumulate(spec.ctypes.data_as(C.c_void_p), C.c_longlong(R), C.c_int(F), C.c_int(Cn),
-                                            acc.ctypes.data_as(C.c_void_p), C.c_int(force_tpw))
-        finally:
-            set_blocked(False)
-    R, F, Cn = spec.shape
-    return lib().emu_csd_accumulate(spec.ctypes.data_as(C.c_void_p), C.c_longlong(R), C.c_int(F), C.c_int(Cn),
-                                    acc.ctypes.data_as(C.c_void_p), C.c_int(force_tpw))
-
-
-def csd_finalize(acc, scale):
-    F, Cn, _ = acc.shape
-    lib().emu_csd_finalize(acc.ctypes.data_as(C.c_void_p), C.c_int(F), C.c_int(Cn), C.c_float(scale))
-
-
-def jack_coh_accumulate(spec, ntaper, S, direct, output, ntrials_total, sum_d, sum_d2):
-    """Emulated spyhip_jack_coh_accumulate (sum_d / sum_d2 float64 in place; sum_d complex128 for 'complex')."""
-    spec = np.ascontiguousarray(spec, dtype=np.complex64)
-    R, F, Cn = spec.shape
-    S = np.ascontiguousarray(S, dtype=np.complex64)
-    direct = np.ascontiguousarray(direct)
-    lib().emu_jack_coh(spec.ctypes.data_as(C.c_void_p), C.c_int(R // ntaper), C.c_int(ntaper), C.c_int(F), C.c_int(Cn),
-                       S.ctypes.data_as(C.c_void_p), direct.ctypes.data_as(C.c_void_p), C.c_int(OUT_KINDS[output]),
-                       C.c_longlong(ntrials_total), sum_d.ctypes.data_as(C.c_void_p), sum_d2.ctypes.data_as(C.c_void_p))
-
-
-def ppc_accumulate(spec, ntaper, acc):
-    """Emulated spyhip_ppc_accumulate: spec (T * ntaper, F, C) complex64, acc (F, C, C) complex64 in place."""
-    spec = np.ascontiguousarray(spec, dtype=np.complex64)
-    R, F, Cn = spec.shape
-    lib().emu_ppc_accumulate(spec.ctypes.data_as(C.c_void_p), C.c_int(R // ntaper), C.c_int(ntaper), C.c_int(F),
-                             C.c_int(Cn), acc.ctypes.data_as(C.c_void_p))
-
-
-def ppc_accumulate_csd(csd, acc):
-    csd = np.ascontiguousarray(csd, dtype=np.complex64)
-    lib().emu_ppc_accumulate_csd(csd.ctypes.data_as(C.c_void_p), C.c_int(csd.shape[0]), C.c_longlong(acc.size),
-                                 acc.ctypes.data_as(C.c_void_p))
-
-
-def ppc_finalize(acc, ntrials, lower_only):
-    F, ni, nj = acc.shape
-    out = np.empty((F, ni, nj), dtype=np.float32)
-    lib().emu_ppc_finalize(acc.ctypes.data_as(C.c_void_p), C.c_int(F), C.c_int(ni), C.c_int(nj),
-                           C.c_int(int(lower_only)), C.c_longlong(ntrials), out.ctypes.data_as(C.c_void_p))
-    return out
-
-
-def ccov_from_accumulator(acc, nsamples, scale, norm=0):
-    """Emulated spyhip_ccov_from_accumulator: acc (nfft/2+1, C, C) complex64 -> (nlag, C, C) float32."""
-    acc = np.ascontiguousarray(acc, dtype=np.complex64)
-    F, Cn, _ = acc.shape
-    L = 2 * (F - 1)
-    tw = np.exp(-2j * np.pi * np.arange(L) / L).astype(np.complex64)
-    nlag = nsamples // 2 + (nsamples & 1)
-    out = np.zeros((nlag, Cn, Cn), dtype=np.float32)
-    rc = lib().emu_ccov(acc.ctypes.data_as(C.c_void_p), tw.ctypes.data_as(C.c_void_p), C.c_int(L), C.c_int(Cn),
-                        C.c_int(nsamples), C.c_double(scale), C.c_int(norm), out.ctypes.data_as(C.c_void_p))
-    assert rc == 0
-    return out
-
-
-def coh_from_accumulator(acc, scale, output="abs"):
-    """Emulated spyhip_coh_from_accumulator (raw lower-triangle accumulator -> coherence)."""
-    F, Cn, _ = acc.shape
-    kind = OUT_KINDS[output]
-    out = np.zeros((F, Cn, Cn), dtype=np.complex64 if kind == 2 else np.float32)
-    lib().emu_coh_from_accumulator(acc.ctypes.data_as(C.c_void_p), C.c_int(F), C.c_int(Cn), C.c_float(scale),
-                                   C.c_int(kind), out.ctypes.data_as(C.c_void_p))
-    return out
-
-
-def coh_normalize(csd, output="abs"):
-    F, Cn, _ = csd.shape
-    kind = OUT_KINDS[output]
-    out = np.empty((F, Cn, Cn), dtype=np.complex64 if kind == 2 else np.float32)
-    lib().emu_coh_normalize(csd.ctypes.data_as(C.c_void_p), C.c_int(F), C.c_int(Cn), C.c_int(kind),
-                            out.ctypes.data_as(C.c_void_p))
-    return out
-
-
 def cwt_exec(data, seg_start, trial_lo, trial_hi, nsig, scales, dt, w0=6.0, detrend=-1, output="pow", tpos=None,
              ntime_out=None, chan_idx=None, accumulate=0, family=None, order=None, sl_cycles=None, direct=True,
              precision64=False, num_cu=None, stage_budget=None, work_budget=None, out=None, trace=None):

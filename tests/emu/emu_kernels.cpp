@@ -15,13 +15,6 @@ thread_local BlockCtx* t_ctx = nullptr;
 #include "../../include/spyhip.h"
 #include "../../syncopy_amd/csrc/mtmfft_kernel.h"
 #include "../../syncopy_amd/csrc/mtmfft_generic.h"
-#include "../../syncopy_amd/csrc/csd_route.h"
-#include "emu_m3_widths.h"
-#include "../../syncopy_amd/csrc/csd_kernel.h"
-#include "../../syncopy_amd/csrc/csd3m_kernel.h"
-#include "../../syncopy_amd/csrc/ppc_kernel.h"
-#include "../../syncopy_amd/csrc/ccov_kernel.h"
-#include "../../syncopy_amd/csrc/jack_kernel.h"
 #include "../../syncopy_amd/csrc/mtmfft2_kernel.h"
 #include "../../syncopy_amd/csrc/mtmfft_blue_kernel.h"
 #include "../../syncopy_amd/csrc/mtmfft_mixed.h"
@@ -43,17 +36,6 @@ void set_error(const char*, ...) {}
 using spyfft::GenPlan;
 using spyfft::MtmArgs;
 
-static int g_blocked = 0;   // channel-blocked hand-over layout for the CSD entry point
-static int g_force_4m = 0;  // SPYHIP_CSD_4M: 256 channels on the 4-multiplication kernel
-static long long g_num_cu = 1LL << 40;  // compute units the CSD route plans for; the default is so many that nothing is re-cut
-
-template <int LOG2N, int G>
-static void emu_launch_ccov(const spyfft::CcovArgs& a) {
-    using C = spyfft::Cfg2<LOG2N, G>;
-    const long long grid = 8 * (((a.npairs + 2 * G - 1) / (2 * G) + 7) / 8);
-    emu::launch(dim3((unsigned)grid), dim3(C::NTHREADS), C::LDS_BYTES, [&] { spyfft::ccov_lags_kernel<LOG2N, G>(a); });
-}
-
 // plus4_kernel<LOG2L> with the grid, threads and LDS of its route (granger_route.h)
 template <int LOG2L>
 void run_plus4(const spywil::PlusRoute& r, const double* g, int F, long long nent, const double* tw, double* gp, double* g0) {
@@ -63,227 +45,6 @@ void run_plus4(const spywil::PlusRoute& r, const double* g, int F, long long nen
 }
 
 extern "C" {
-
-void emu_set_blocked(int on) { g_blocked = on; }
-void emu_set_force_4m(int on) { g_force_4m = on; }
-void emu_set_num_cu(long long n) { g_num_cu = n > 0 ? n : 1LL << 40; }
-
-// spyhip_csd_accumulate for the emulated kernels: the route of csd_route.h (the one csd.hip launches), asked with the
-// emulator's sample of 3M instances and walked with emu::launch.  force_tpw (1, 3, 5) is the test-only override that picks
-// a generic csd_accum_kernel<TA, TB> directly.  Returns a code for the first kernel: 1 / 3 / 5 generic tiles per wave,
-// 6 the instruction-lean path, 7 its wide variant, 8 / 9 the 3M kernel (exact 256 / padded), 10 / 11 the 256-channel
-// block walk (3M / 4M).
-}  // extern "C"
-
-template <int TA, int TB, int FAST = 0>
-static void emu_accum(spycsd::CsdArgs a, const spycsd::AccumGeometry& g, int nsplit = 1) {
-    a.kb = g.kb;
-    if (g.grid > 0)
-        emu::launch(dim3((unsigned)g.grid, (unsigned)nsplit), dim3(spycsd::CSD_THREADS), g.lds,
-                    [&] { spycsd::csd_accum_kernel<TA, TB, FAST>(a); });
-}
-
-static void emu_accum(const spycsd::CsdArgs& a, int ta, int fast, const spycsd::AccumGeometry& g) {
-    switch (ta * 10 + fast) {
-        case 50: emu_accum<5, 4>(a, g); break;
-        case 51: emu_accum<5, 4, 1>(a, g); break;
-        case 52: emu_accum<5, 4, 2>(a, g); break;
-        case 53: emu_accum<5, 4, 3>(a, g); break;
-        case 30: emu_accum<3, 2>(a, g); break;
-        default: emu_accum<1, 1>(a, g); break;
-    }
-}
-
-// grid of m3_launch_one (csd3m_launch_impl.h)
-template <int CH, bool EXACT, bool RECT = false, bool M4 = false>
-static void emu_m3(spycsd::CsdArgs a, long long nprow) {
-    constexpr int NP = spycsd::M3Tab<CH, RECT>::NP;
-    a.item_base = 0;
-    a.item_end = nprow * spycsd::M3_TILES_PER_F;
-    const long long grid = NP > 1 ? ((nprow + 7) / 8) * 8 * NP : (a.blocked ? ((nprow + 31) / 32) * 32 : nprow);
-    if (nprow > 0)
-        emu::launch(dim3((unsigned)grid), dim3(512), spycsd::M3_LDS_BYTES, [&] { spycsd::csd3m_kernel<CH, 8, EXACT, RECT, M4>(a); });
-}
-
-extern "C" {
-
-int emu_csd_accumulate(const float* spec, long long nrows, int F, int C, float* acc, int force_tpw) {
-    using spycsd::StepKind;
-    spycsd::CsdQuery q;
-    q.nchan = C; q.nfreq = F; q.nrows = nrows;
-    q.blocked = g_blocked != 0;
-    q.phase_exact = g_force_4m != 0;
-    q.num_cu = g_num_cu;
-    q.have_m3 = emu_have_m3;
-    spycsd::CsdArgs base{};
-    base.F = F; base.C = C;
-    base.acc = reinterpret_cast<float2*>(acc);
-    base.blocked = g_blocked;
-    if (force_tpw) {                             // (asks no route: a shape the route refuses still reaches the generic kernel)
-        const int ta = force_tpw, tb = force_tpw == 1 ? 1 : force_tpw - 1;
-        if (ta != 1 && ta != 3 && ta != 5) return -1;
-        if (nrows < 0 || F < 1 || C < 1) return -1;
-        base.nt = (C + 31) / 32; base.ntiles = (int)spycsd::tri_tiles(C); base.cpad = base.nt * 32;
-        base.nitems = (long long)F * base.ntiles;
-        base.spec = reinterpret_cast<const float2*>(spec);
-        base.nrows = nrows;
-        base.item_end = base.nitems;
-        const spycsd::AccumGeometry g = spycsd::accum_geometry(ta, tb, 0, base.ntiles, base.cpad, F, nrows, 0, 0, q.lds_per_block, base.nitems);
-        if (g.err) return g.err;
-        if (nrows > 0) emu_accum(base, ta, 0, g);
-        return ta;
-    }
-    const spycsd::CsdRoute r = spycsd::csd_route(q);
-    if (r.err) return r.err;
-    base.nt = r.nt; base.ntiles = r.ntiles; base.nitems = r.nitems; base.cpad = r.cpad;
-    base.fast_per = r.fast_per; base.fast_nwgf = r.fast_nwgf;
-    for (const spycsd::CsdStep& s : r.steps) {
-        spycsd::CsdArgs a = base;
-        a.spec = reinterpret_cast<const float2*>(spec) + (size_t)s.row0 * F * C;
-        a.nrows = s.nrows;
-        a.item_base = s.item0; a.item_end = s.item1;
-        a.ctot = s.n0 ? C : 0;
-        a.ch0 = s.ch0; a.n0 = s.n0; a.ch1 = s.ch1; a.n1 = s.n1;
-        switch (s.kind) {
-            case StepKind::ACCUM: emu_accum(a, s.ta, s.fast, s.geo); break;
-            case StepKind::TAIL: {               // launch_tail of csd.hip with the scratch on the host
-                const int f0 = (int)(s.item0 / r.ntiles), nf = F - f0, nsplit = s.split.nsplit;
-                const long long n = (long long)nf * C * C;
-                std::vector<float2> part(nsplit > 1 ? (size_t)(nsplit - 1) * n : 0);
-                if (nsplit > 1) { a.rows_per_split = s.split.rows_per_split; a.part = part.data(); a.part_f0 = f0; a.part_nf = nf; }
-                emu_accum<1, 1>(a, s.geo, nsplit);
-                if (nsplit > 1)
-                    emu::launch(dim3((unsigned)std::min<long long>((n + 255) / 256, 4096)), dim3(256), 0,
-                                [&] { spycsd::csd_reduce_parts_kernel(a.acc, a.part, nsplit - 1, f0, nf, C); });
-                break;
-            }
-            case StepKind::M3_EXACT: emu_m3<256, true>(a, s.nprow); break;
-            case StepKind::M3_PADDED:
-                switch (s.chp) {
-#define EMU_M3(CH) case CH: emu_m3<CH, false>(a, s.nprow); break;
-                    EMU_M3_WIDTHS(EMU_M3)
-#undef EMU_M3
-                    default: return -1;            // (the route asked emu_have_m3, which reads the same list)
-                }
-                break;
-            case StepKind::M4_BLOCK: emu_m3<256, false, false, true>(a, s.nprow); break;
-            case StepKind::M3_RECT: emu_m3<512, false, true>(a, s.nprow); break;
-            case StepKind::M4_RECT: emu_m3<512, false, true, true>(a, s.nprow); break;
-            case StepKind::RANK1:                // csd_rank1_kernel of csd.hip, on the host
-                for (int f = 0; f < F; ++f)
-                    for (int i = 0; i < C; ++i)
-                        for (int j = 0; j <= i; ++j) {
-                            const float2 u = a.spec[(size_t)f * C + i], v = a.spec[(size_t)f * C + j];
-                            float2& o = a.acc[((size_t)f * C + i) * C + j];
-                            o.x += u.x * v.x + u.y * v.y;
-                            o.y += u.y * v.x - u.x * v.y;
-                        }
-                break;
-        }
-    }
-    if (r.steps.empty()) return 0;
-    const spycsd::CsdStep& s0 = r.steps.front();
-    switch (s0.kind) {
-        case StepKind::ACCUM: return s0.fast == 3 ? 7 : s0.fast ? 6 : s0.ta;
-        case StepKind::M3_EXACT: return 8;
-        case StepKind::M3_PADDED: return s0.n0 ? 10 : 9;
-        case StepKind::M4_BLOCK: return 11;
-        case StepKind::RANK1: return g_force_4m ? 11 : 10;
-        default: return -1;
-    }
-}
-
-void emu_csd_finalize(float* acc, int F, int C, float scale) {
-    emu::launch(dim3((unsigned)(F * spycsd::tri_tiles(C))), dim3(256), 0,
-                [&] { spycsd::csd_finalize_kernel(reinterpret_cast<float2*>(acc), F, C, scale); });
-}
-
-void emu_coh_from_accumulator(const float* acc, int F, int C, float scale, int kind, void* out) {
-    const dim3 grid((unsigned)(F * spycsd::tri_tiles(C)));
-    if (kind == SPYHIP_OUT_FOURIER)
-        emu::launch(grid, dim3(256), 0, [&] { spycsd::coh_from_acc_kernel<true>(reinterpret_cast<const float2*>(acc), F, C, scale, kind, out); });
-    else
-        emu::launch(grid, dim3(256), 0, [&] { spycsd::coh_from_acc_kernel<false>(reinterpret_cast<const float2*>(acc), F, C, scale, kind, out); });
-}
-
-void emu_coh_normalize(const float* csd, int F, int C, int kind, void* out) {
-    if (kind == SPYHIP_OUT_FOURIER)
-        emu::launch(dim3(4), dim3(256), 0, [&] { spycsd::coh_normalize_kernel<true>(reinterpret_cast<const float2*>(csd), F, C, kind, out); });
-    else
-        emu::launch(dim3(4), dim3(256), 0, [&] { spycsd::coh_normalize_kernel<false>(reinterpret_cast<const float2*>(csd), F, C, kind, out); });
-}
-
-// K9 (mirrors spyhip_jack_coh_accumulate)
-void emu_jack_coh(const float* spec, int ntrials, int K, int F, int C, const float* S, const void* direct, int kind,
-                  long long T, double* sum_d, double* sum_d2) {
-    spycsd::JackArgs a{};
-    a.spec = reinterpret_cast<const float2*>(spec);
-    a.S = reinterpret_cast<const float2*>(S);
-    a.direct = direct;
-    a.ntrials = ntrials; a.K = K; a.F = F; a.C = C; a.kind = kind;
-    a.T = (float)T;
-    a.sum_d = sum_d; a.sum_d2 = sum_d2;
-    const int nt = (C + 31) / 32;
-    const size_t lds = 2 * (size_t)2 * K * 32 * sizeof(float2);
-    const dim3 grid((unsigned)(8 * ((F + 7) / 8) * (nt * (nt + 1) / 2)));
-    if (kind == SPYHIP_OUT_FOURIER) emu::launch(grid, dim3(256), lds, [&] { spycsd::jack_coh_kernel<true>(a); });
-    else emu::launch(grid, dim3(256), lds, [&] { spycsd::jack_coh_kernel<false>(a); });
-}
-
-// K7 (mirrors ppc.hip)
-void emu_ppc_accumulate(const float* spec, int ntrials, int ntaper, int F, int C, float* acc) {
-    spyppc::PpcArgs a{};
-    a.spec = reinterpret_cast<const float2*>(spec);
-    a.ntrials = ntrials; a.ntaper = ntaper; a.F = F; a.C = C;
-    a.acc = reinterpret_cast<float2*>(acc);
-    const int nt = (C + 31) / 32;
-    const size_t lds = 2 * (size_t)2 * ntaper * 32 * sizeof(float2);
-    emu::launch(dim3((unsigned)(8 * ((F + 7) / 8) * (nt * (nt + 1) / 2))), dim3(256), lds, [&] { spyppc::ppc_accum_kernel(a); });
-}
-
-void emu_ppc_accumulate_csd(const float* csd, int ntrials, long long n, float* acc) {
-    emu::launch(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, [&] {
-        spyppc::ppc_accum_csd_kernel(reinterpret_cast<const float2*>(csd), n, ntrials, reinterpret_cast<float2*>(acc));
-    });
-}
-
-void emu_ppc_finalize(const float* acc, int F, int ni, int nj, int lower_only, long long T, float* out) {
-    const long long n = (long long)F * ni * nj;
-    emu::launch(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, [&] {
-        spyppc::ppc_finalize_kernel(reinterpret_cast<const float2*>(acc), F, ni, nj, lower_only, (double)T, out);
-    });
-}
-
-// K8 (mirrors ccov.hip): tw = exp(-2 pi i m / L) from the caller; norm as spyhip_ccov_from_accumulator
-int emu_ccov(const float* acc, const float* tw, int nfft, int nchan, int nsamples, double scale, int norm, float* out) {
-    spyfft::CcovArgs a{};
-    a.acc = reinterpret_cast<const float2*>(acc);
-    a.tw = reinterpret_cast<const float2*>(tw);
-    a.C = nchan; a.nsamples = nsamples;
-    a.nlag = nsamples / 2 + (nsamples & 1);
-    a.q = (nsamples & 1) ? 0 : 1;
-    a.npairs = (long long)nchan * (nchan + 1) / 2;
-    a.scale = (float)(scale / (double)nfft);
-    a.out = out;
-    switch (nfft) {
-        case 1024: emu_launch_ccov<10, 4>(a); break;
-        case 2048: emu_launch_ccov<11, 2>(a); break;
-        case 4096: emu_launch_ccov<12, 1>(a); break;
-        case 8192: emu_launch_ccov<13, 1>(a); break;
-        default: return -1;
-    }
-    if (norm) {
-        std::vector<float> d(nchan);
-        const float dc = (float)(scale / ((double)nsamples * (double)nsamples));
-        emu::launch(dim3((nchan + 255) / 256), dim3(256), 0,
-                    [&] { spyfft::ccov_diag_kernel(out, a.acc, nchan, norm, dc, d.data()); });
-        const long long n = (long long)a.nlag * nchan * nchan;
-        emu::launch(dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                    [&] { spyfft::ccov_normalize_kernel(out, n, nchan, d.data()); });
-    }
-    return 0;
-}
-
 // spyhip_cwt_plan_create* + set_direct / set_precision + spyhip_cwt_exec for the emulated kernels: the taps, the plan and the
 // steps of cwt_route.h (the ones cwt.hip uploads and launches), walked with emu::launch on host buffers.  family, p0, p1:
 // spycwt::sample_taps; num_cu and the two byte budgets as spycwt::ExecQuery (<= 0: the library's).  `trace`: one line per

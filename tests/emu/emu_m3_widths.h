@@ -1,6 +1,6 @@
 // The padded 3M instances csd3m_kernel<CH, 8, false> the kernel emulator builds (TEST INFRASTRUCTURE ONLY): a sample of
 // the multiples of 16 up to 512 that the library holds.  The one list behind the emulator's "is it built" answer, its
-// dispatch switch (emu_kernels.cpp) and the route shim's sample (csd_route_shim.cpp).
+// dispatch switch (csd_emu.cpp) and the route shim's sample (csd_route_shim.cpp).
 #pragma once
 
 #define EMU_M3_WIDTHS(X) X(16) X(32) X(48) X(64) X(96) X(128) X(192) X(240) X(256) X(304) X(320) X(384)

@@ -1,15 +1,16 @@
 // Stand-in for <hip/hip_runtime.h>, TEST INFRASTRUCTURE ONLY (see ../hip_emu.h).  With tests/emu first on the include
 // path the library's own .hip files compile as C++: their launchers run on the CPU and their kernels under emu::launch.
-// It names what the host code of the preprocessing, statistics, covariance, resampling, histogram and Hilbert launchers
-// (and csrc/spy_common.h under them) uses of the runtime, nothing else; "device" memory is host memory and the one
-// stream is synchronous.  Define one translation unit per emulator library: the launch log below lives in it.
+// It names what the host code of the preprocessing, statistics, covariance, resampling, histogram, Hilbert, cross-spectral,
+// phase-consistency and lag launchers (and csrc/spy_common.h under them) uses of the runtime, nothing else; "device"
+// memory is host memory and the one stream is synchronous.  Define one translation unit per emulator library: the launch log below lives in it.
 #pragma once
 #include "../hip_emu.h"
 
 typedef struct emuStream* hipStream_t;
 typedef struct emuEvent* hipEvent_t;
 enum hipError_t { hipSuccess = 0, hipErrorOutOfMemory = 2 };
-enum hipMemcpyKind { hipMemcpyHostToDevice = 1 };
+enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2 };
+enum { hipEventDisableTiming = 2 };
 enum hipFuncAttribute { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
 inline hipError_t hipSetDevice(int) { return hipSuccess; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
@@ -18,6 +19,10 @@ inline hipError_t hipMalloc(void** p, size_t bytes) { return (*p = std::malloc(b
 inline hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
 inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind, hipStream_t) { std::memcpy(dst, src, bytes); return hipSuccess; }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+inline hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t) { std::memset(dst, value, bytes); return hipSuccess; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { static char one; *e = reinterpret_cast<hipEvent_t>(&one); return hipSuccess; }
+inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
 inline hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
 
 // ---- the launch log: grid, block and dynamic LDS bytes of every launch since the last reset, for the tests that assert

@@ -5,6 +5,7 @@ parity tests proper."""
 import numpy as np
 import pytest
 
+import csd_drive as D
 import emu_driver as E
 import jack_oracle as JO
 from oracle import spy_oracle as O
@@ -86,8 +87,8 @@ def test_blocked_handover_layout(C, N, B, K):
     a_blk = np.zeros((F, C, C), np.complex64)
     # the blocked hand-over is served by the 4-multiplication kernels only: compare like with like (the standard
     # layout would otherwise take the 3-multiplication kernel, whose rounding differs in the last bit)
-    E.csd_accumulate(std.reshape(B * K, F, C), a_std, force_4m=True)
-    E.csd_accumulate(np.ascontiguousarray(blk), a_blk, blocked=True)
+    D.csd_accumulate(std.reshape(B * K, F, C), a_std, force_4m=True)
+    D.csd_accumulate(np.ascontiguousarray(blk), a_blk, blocked=True)
     np.testing.assert_array_equal(a_std, a_blk)
 
 
@@ -230,17 +231,17 @@ def test_csd_mfma_kernel(C, F, R, tpw):
     rng = np.random.default_rng(C)
     spec = (rng.normal(size=(R, F, C)) + 1j * rng.normal(size=(R, F, C))).astype(np.complex64)
     acc = np.zeros((F, C, C), np.complex64)
-    E.csd_accumulate(spec[:R // 2], acc, tpw)
-    E.csd_accumulate(spec[R // 2:], acc, tpw)
-    fused = {o: E.coh_from_accumulator(acc, 1.0 / R, o) for o in ("abs", "complex")}
-    E.csd_finalize(acc, 1.0 / R)
+    D.csd_accumulate(spec[:R // 2], acc, tpw)
+    D.csd_accumulate(spec[R // 2:], acc, tpw)
+    fused = {o: D.coh_from_accumulator(acc, 1.0 / R, o) for o in ("abs", "complex")}
+    D.csd_finalize(acc, 1.0 / R)
     for o, got in fused.items():                       # fused K5 = finalize + normalize, bit for bit
-        np.testing.assert_array_equal(got, E.coh_normalize(acc, o))
+        np.testing.assert_array_equal(got, D.coh_normalize(acc, o))
     ref = (np.einsum("rfi,rfj->fij", spec.astype(np.complex128), spec.conj().astype(np.complex128)) / R)
     assert_parity(acc, ref.astype(np.complex64), what="csd")
     assert np.array_equal(acc, acc.conj().transpose(0, 2, 1)) and np.all(acc.imag[:, range(C), range(C)] == 0)
     for output in ("abs", "pow", "complex", "imag"):
-        assert_parity(E.coh_normalize(acc, output), O.normalize_csd(acc, output), what=output)
+        assert_parity(D.coh_normalize(acc, output), O.normalize_csd(acc, output), what=output)
 
 
 @pytest.mark.parametrize("C,F,R", [(256, 2, 7), (128, 5, 9), (64, 6, 9), (192, 2, 6), (320, 1, 6),
@@ -260,9 +261,9 @@ def test_csd_3m_kernel(C, F, R):
     common = rng.normal(size=(R, F, 1)) + 1j * rng.normal(size=(R, F, 1))
     spec = ((rng.normal(size=(R, F, C)) + 1j * rng.normal(size=(R, F, C)) + 2.0 * common) * gain).astype(np.complex64)
     acc = np.zeros((F, C, C), np.complex64)
-    assert E.csd_accumulate(spec[:R // 2], acc) == code and E.csd_accumulate(spec[R // 2:], acc) == code
+    assert D.csd_accumulate(spec[:R // 2], acc) == code and D.csd_accumulate(spec[R // 2:], acc) == code
     acc4 = np.zeros((F, C, C), np.complex64)
-    assert E.csd_accumulate(spec, acc4, force_4m=True) != code
+    assert D.csd_accumulate(spec, acc4, force_4m=True) != code
     ref = np.einsum("rfi,rfj->fij", spec.astype(np.complex128), spec.conj().astype(np.complex128))
     ii, jj = np.tril_indices(C)
     # element-wise against the exact product: the error scale of an entry is sqrt(S_ii S_jj), not the global maximum
@@ -271,7 +272,7 @@ def test_csd_3m_kernel(C, F, R):
         err = np.abs(got[:, ii, jj] - ref[:, ii, jj]) / scale
         assert err.max() < 3e-6, err.max()
     assert_parity(acc[:, ii, jj], ref[:, ii, jj].astype(np.complex64), what="3M csd, lower triangle")
-    E.csd_finalize(acc, 1.0 / R)
+    D.csd_finalize(acc, 1.0 / R)
     assert np.array_equal(acc, acc.conj().transpose(0, 2, 1)) and np.all(acc.imag[:, range(C), range(C)] == 0)
     assert_parity(acc, (ref / R).astype(np.complex64), what="3M csd finalised")
 
@@ -288,9 +289,11 @@ def test_csd_recut_tail(C, F, R, force_4m, code):
     rng = np.random.default_rng(C + R)
     spec = (rng.normal(size=(R, F, C)) + 1j * rng.normal(size=(R, F, C))).astype(np.complex64)
     acc = np.zeros((F, C, C), np.complex64)
-    assert E.csd_accumulate(spec, acc, force_4m=force_4m, num_cu=4) == code
+    assert D.csd_accumulate(spec, acc, force_4m=force_4m, num_cu=4) == code
+    log = D.launches()            # the main launch, then the tail: one launch, or its rows over blockIdx.y + the reduction
+    assert [tuple(r[[1, 3]]) for r in log[1:]] == ([(3, 512), (1, 256)] if R == 130 else [(1, 512)])
     whole = np.zeros((F, C, C), np.complex64)
-    E.csd_accumulate(spec, whole, force_4m=force_4m)              # no tail: the last frequencies in the main launch
+    D.csd_accumulate(spec, whole, force_4m=force_4m)              # no tail: the last frequencies in the main launch
     ref = np.einsum("rfi,rfj->fij", spec.astype(np.complex128), spec.conj().astype(np.complex128))
     ii, jj = np.tril_indices(C)
     assert_parity(acc[:, ii, jj], ref[:, ii, jj].astype(np.complex64), what="csd with a re-cut tail, lower triangle")
@@ -311,15 +314,15 @@ def test_ppc_kernel(C, F, T, K):
     ref = O.ppc(st)[0]
     first = 1 if (C, F, T, K) in JO.PPC_EDGE_CASES else 2
     U = np.zeros((F, C, C), np.complex64)
-    E.ppc_accumulate(spec[:first].reshape(-1, F, C), K, U)
-    E.ppc_accumulate(spec[first:].reshape(-1, F, C), K, U)
-    got = E.ppc_finalize(U, T, True)
+    D.ppc_accumulate(spec[:first].reshape(-1, F, C), K, U)
+    D.ppc_accumulate(spec[first:].reshape(-1, F, C), K, U)
+    got = D.ppc_finalize(U, T, True)
     print(f"ppc {C}-{F}-{T}-{K}: err/tol {excess(got, ref, rtol=1e-4, atol_rel=2e-5):.3f}")
     assert_parity(got, ref, what="ppc", rtol=1e-4, atol_rel=2e-5)
     assert np.array_equal(got, got.transpose(0, 2, 1)) and np.allclose(got[:, C - 1], 1, atol=1e-6)
     U2 = np.zeros((F, C, C), np.complex64)
-    E.ppc_accumulate_csd(st, U2)
-    assert_parity(E.ppc_finalize(U2, T, False), ref, what="ppc from csd", rtol=1e-4, atol_rel=2e-5)
+    D.ppc_accumulate_csd(st, U2)
+    assert_parity(D.ppc_finalize(U2, T, False), ref, what="ppc from csd", rtol=1e-4, atol_rel=2e-5)
 
 
 @pytest.mark.parametrize("C,F,T,K,output", [(5, 3, 6, 3, "abs"), (40, 2, 5, 2, "complex"), (33, 1, 4, 1, "imag")])
@@ -334,8 +337,8 @@ def test_jackknife_coherence_kernel(C, F, T, K, output):
     direct = O.normalize_csd(S.astype(np.complex64)[None], output)[0]
     sum_d = np.zeros((F, C, C), np.complex128 if output == "complex" else np.float64)
     sum_d2 = np.zeros((F, C, C), np.float64)
-    E.jack_coh_accumulate(spec[:2].reshape(-1, F, C), K, S, direct, output, T, sum_d, sum_d2)
-    E.jack_coh_accumulate(spec[2:].reshape(-1, F, C), K, S, direct, output, T, sum_d, sum_d2)
+    D.jack_coh_accumulate(spec[:2].reshape(-1, F, C), K, S, direct, output, T, sum_d, sum_d2)
+    D.jack_coh_accumulate(spec[2:].reshape(-1, F, C), K, S, direct, output, T, sum_d, sum_d2)
     rd, rd2 = np.zeros_like(sum_d), np.zeros_like(sum_d2)
     for t in range(T):
         loo = ((T * S - st[t]) / (T - 1)).astype(np.complex64)
@@ -357,7 +360,7 @@ def test_jackknife_coherence_kernel_dispatch_edges(case):
     sum_d2 = np.zeros((F, C, C), np.float64)
     t0 = 0
     for n in split:
-        E.jack_coh_accumulate(spec[t0:t0 + n].reshape(-1, F, C), K, S, direct, kind, T, sum_d, sum_d2)
+        D.jack_coh_accumulate(spec[t0:t0 + n].reshape(-1, F, C), K, S, direct, kind, T, sum_d, sum_d2)
         t0 += n
     assert t0 == T
     JO.check(sum_d, sum_d2, m, kind, "K9 emulated " + JO.case_id(case))
@@ -378,7 +381,7 @@ def test_ccov_kernel(C, N, norm):
         L *= 2
     X = np.fft.rfft(x.astype(np.float64), n=L, axis=1).astype(np.complex64)          # (T, F, C)
     acc = np.einsum("tfa,tfb->fab", X, X.conj()).astype(np.complex64)
-    got = E.ccov_from_accumulator(acc, N, 1.0 / T, norm)
+    got = D.ccov_from_accumulator(acc, N, 1.0 / T, norm)
     ref = np.mean([O.cross_covariance(t, 1.0, None, norm == 2)[0] for t in x], axis=0)
     if norm == 1:
         ref = O.normalize_ccov(ref)
@@ -1077,7 +1080,8 @@ def test_csd_3m_more_than_512_channels():
     rng = np.random.default_rng(3)
     spec = (rng.normal(size=(R, F, C)) + 1j * rng.normal(size=(R, F, C))).astype(np.complex64)
     acc = np.zeros((F, C, C), np.complex64)
-    assert E.csd_accumulate(spec[:2], acc) == 10 and E.csd_accumulate(spec[2:], acc) == 10
+    few = dict(workgroups=8)          # the rank-1 update strides over 8 workgroups (of 256 OS threads each here), not 1061
+    assert D.csd_accumulate(spec[:2], acc, **few) == 10 and D.csd_accumulate(spec[2:], acc, **few) == 10
     ref = np.einsum("rfi,rfj->fij", spec.astype(np.complex128), spec.conj().astype(np.complex128))
     ii, jj = np.tril_indices(C)
     assert_parity(acc[:, ii, jj], ref[:, ii, jj].astype(np.complex64), what="wide csd, lower triangle")
@@ -1086,12 +1090,12 @@ def test_csd_3m_more_than_512_channels():
     assert not acc[:, iu[off], ju[off]].any()            # nothing else lands above the diagonal
     # phase-exact accumulation: the same walk with the 4-multiplication instances (csd3m_kernel<..., M4 = true>)
     acc4 = np.zeros((F, C, C), np.complex64)
-    assert E.csd_accumulate(spec, acc4, force_4m=True) == 11
+    assert D.csd_accumulate(spec, acc4, force_4m=True, **few) == 11
     assert_parity(acc4[:, ii, jj], ref[:, ii, jj].astype(np.complex64), what="wide csd, 4 multiplications")
     # its imaginary part is a sum of products, not a difference of the three 3M products: error ~ eps * |Im| terms only
     coherent = np.repeat(spec[:, :, :1], C, axis=2) * (1 + 1e-3 * rng.normal(size=(1, 1, C))).astype(np.float32)
     acc4[:] = 0
-    E.csd_accumulate(coherent.astype(np.complex64), acc4, force_4m=True)
+    D.csd_accumulate(coherent.astype(np.complex64), acc4, force_4m=True, **few)
     scale = np.abs(acc4[0, 0, 0])
     assert np.abs(acc4[:, ii, jj].imag).max() <= 1e-6 * scale       # real multiples of one signal: Im = 0 up to rounding
 
