@@ -644,6 +644,29 @@ int spyhip_select(spyhip_ctx* ctx, int elem_bytes, const void* src_d, int64_t sr
                   const int32_t* idx_d, const int64_t* desc, const int64_t* desc_d, int64_t ntrials, void* out_d,
                   int64_t out_rows);
 
+/* ---- channel concatenation (datatype/concat.py; datatype/methods/concat.py: concat, concat_cF).
+ * out = the rows of nsrc tensors (2 .. SPYHIP_CONCAT_MAX) side by side, in one launch.  Source s is src_rows[s] rows
+ * (time is the slowest axis of every data class) of `pre` lines of run[s] elements of elem_bytes bytes (4, 8 or 16),
+ * C-order; an output row is `pre` lines of W = run[0] + ... + run[nsrc - 1] elements, and in every line the run of
+ * source s begins at element run[0] + ... + run[s - 1].  Elements move as raw bits, so NaN payloads and signed zeros
+ * arrive unchanged.  Channel as the fastest axis: pre = the product of the axes between time and channel, run[s] = the
+ * channels of s; channel in the middle: pre = 1, run[s] = channels x the axes behind them.  src_d, src_rows and run are
+ * host arrays of nsrc entries (src_d: device pointers).  `desc` holds 2 + nsrc int64 per trial: the first output row,
+ * the trial's rows, and the first row in each source.  The output rows of the trials follow each other; the source rows
+ * may repeat, overlap and come in any order, and a trial may have no rows.  desc is the host copy, which is checked
+ * before anything runs, desc_d the same table on the device.  -1 for nsrc outside 2 .. SPYHIP_CONCAT_MAX, an element
+ * size other than 4, 8 or 16, pre < 1 or a run < 1, a trial outside a source or outside out_rows, output rows that are
+ * not stacked, an output that is or overlaps a source, a tensor too large for 64-bit byte offsets, and a base that is
+ * not aligned to its element type (8 bytes for 16-byte elements).
+ * A lane moves 16 bytes where every run[s] * elem_bytes is a multiple of 16 and every base address lies on a 16-byte
+ * boundary (every line and run offset then does too), else one element.  Consecutive lanes take consecutive output
+ * addresses and every output byte is written exactly once.  Asynchronous on the context's stream; nothing is
+ * allocated, no atomics, no LDS. */
+#define SPYHIP_CONCAT_MAX 8
+int spyhip_concat(spyhip_ctx* ctx, int elem_bytes, int nsrc, const void* const* src_d, const int64_t* src_rows,
+                  const int64_t* run, int64_t pre, const int64_t* desc, const int64_t* desc_d, int64_t ntrials,
+                  void* out_d, int64_t out_rows);
+
 #ifdef __cplusplus
 }
 #endif

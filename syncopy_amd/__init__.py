@@ -21,7 +21,8 @@ _LAZY = {"freqanalysis": ".specest.freqanalysis", "connectivityanalysis": ".conn
          "median": ".statistics.summary_stats", "itc": ".statistics.summary_stats",
          "preprocessing": ".preproc.preprocessing", "resampledata": ".preproc.resampledata",
          "timelockanalysis": ".statistics.timelockanalysis", "spike_psth": ".statistics.spike_psth",
-         "selectdata": ".datatype.selectdata", "copy": ".datatype.selectdata", "redefinetrial": ".datatype.redefinetrial"}
+         "selectdata": ".datatype.selectdata", "copy": ".datatype.selectdata", "redefinetrial": ".datatype.redefinetrial",
+         "concat": ".datatype.concat"}
 
 
 def release_device_buffers():

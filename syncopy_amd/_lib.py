@@ -127,6 +127,8 @@ SIGNATURES = {
                                vp, C.c_int64]),
     "spyhip_select": (C.c_int, [vp, C.c_int, vp, C.c_int64, c_i64p, c_i32p, c_i64p, c_i64p, c_i32p, vp, c_i64p, vp,
                                 C.c_int64, vp, C.c_int64]),
+    "spyhip_concat": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp), c_i64p, c_i64p, C.c_int64, c_i64p, vp, C.c_int64,
+                                vp, C.c_int64]),
 }
 
 

@@ -408,6 +408,52 @@ class Device:
             for b in bufs:
                 b.free()
 
+    # ---- channel concatenation
+    def concat(self, sources, trials=None, pre=1):
+        """The trials of 2 .. 8 arrays side by side, stacked: `sources` are arrays of one dtype (elements of 4, 8 or 16
+        bytes) whose first axis are the rows and whose rows are `pre` lines; `trials` (nsources, T, 2) are the [start, stop)
+        rows of trial t in each source (the same length in all of them; default: every source whole, one trial).  In every
+        line of the result the line of source s follows that of source s - 1: with pre = 1 what
+        `np.concatenate([np.concatenate([x[a:b].reshape(b - a, -1) ...], axis=1) ...])` gives, bit for bit, as a matrix
+        of rows.  See spyhip_concat in include/spyhip.h."""
+        sources = [np.ascontiguousarray(x) for x in sources]
+        nsrc, pre = len(sources), int(pre)
+        if nsrc < 2 or any(x.ndim < 1 or x.dtype != sources[0].dtype for x in sources) or pre < 1:
+            raise ValueError("sources must be two or more arrays of one dtype")
+        dtype = sources[0].dtype
+        if trials is None:
+            trials = [[[0, x.shape[0]]] for x in sources]
+        trl = np.asarray(trials, dtype=np.int64).reshape(nsrc, -1, 2)
+        n = trl[0, :, 1] - trl[0, :, 0]
+        if np.any(n < 0) or np.any(trl[:, :, 1] - trl[:, :, 0] != n) or np.any(trl[:, :, 0] < 0) or \
+                any(np.any(trl[s, :, 1] > x.shape[0]) for s, x in enumerate(sources)):
+            raise ValueError("every source must hold the rows of every trial, and a trial has the same rows in all of them")
+        width = [int(np.prod(x.shape[1:], dtype=np.int64)) for x in sources]
+        if any(w % pre or w == 0 for w in width):
+            raise ValueError("every source's rows must be `pre` lines")
+        starts = np.concatenate(([0], np.cumsum(n))).astype(np.int64)
+        desc = np.ascontiguousarray(np.concatenate([starts[:-1, None], n[:, None], trl[:, :, 0].T], axis=1))
+        shape = (int(starts[-1]), sum(width))
+        if shape[0] == 0:
+            return np.empty(shape, dtype=dtype)
+        run = np.array([w // pre for w in width], dtype=np.int64)
+        rows = np.array([x.shape[0] for x in sources], dtype=np.int64)
+        bufs = []
+        try:
+            for x in sources:
+                bufs.append(self._put(x, dtype))
+            ptrs = (C.c_void_p * nsrc)(*[b.ptr.value for b in bufs])
+            out, desc_d = Buffer(self, shape, dtype), self._put(desc, np.int64)
+            bufs += [out, desc_d]
+            check(self.lib.spyhip_concat(self.handle, dtype.itemsize, nsrc, ptrs, rows.ctypes.data_as(_lib.c_i64p),
+                                         run.ctypes.data_as(_lib.c_i64p), pre, desc.ctypes.data_as(_lib.c_i64p), desc_d.ptr,
+                                         desc.shape[0], out.ptr, shape[0]), "spyhip_concat")
+            return out.numpy()
+        finally:
+            self.synchronize()
+            for b in bufs:
+                b.free()
+
     def close(self):
         if self.handle is not None:
             self.lib.spyhip_ctx_destroy(self.handle)

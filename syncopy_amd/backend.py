@@ -1528,3 +1528,30 @@ def select(src, desc, out, axes=None):
                                 desc.ctypes.data_as(_lib.c_i64p), _ptr(desc_d), desc.shape[0], _ptr(out), int(out.shape[0])),
           "spyhip_select")
     return out
+
+
+# ---- channel concatenation (csrc/concat.hip) ---------------------------------------------------------------------------
+def concat(sources, desc, out, pre=1):
+    """out = the rows of 2 .. 8 `sources` side by side, for the trials of `desc` ((ntrials, 2 + len(sources)) int64 on the
+    host: output row, rows, the first row in each source; see include/spyhip.h: spyhip_concat), one launch.  sources, out:
+    contiguous tensors of one dtype whose first axis are the rows; a row is `pre` lines, and in every line of `out` the
+    line of source s follows that of source s - 1 (pre = 1: the rows themselves are joined).  A source may be a view into
+    a larger allocation as long as it is contiguous."""
+    nsrc = len(sources)
+    assert out.is_cuda and out.is_contiguous() and out.dim() >= 1 and pre >= 1
+    assert all(s.is_cuda and s.is_contiguous() and s.dtype == out.dtype and s.dim() >= 1 and s.device == out.device
+               for s in sources)
+    desc = np.ascontiguousarray(desc, dtype=np.int64).reshape(-1, 2 + nsrc)
+    if desc.shape[0] == 0 or out.numel() == 0:
+        return out
+    width = [int(np.prod(s.shape[1:], dtype=np.int64)) for s in sources]
+    assert all(w % pre == 0 for w in width) and int(np.prod(out.shape[1:], dtype=np.int64)) == sum(width)
+    run = np.array([w // pre for w in width], dtype=np.int64)
+    rows = np.array([int(s.shape[0]) for s in sources], dtype=np.int64)
+    ptrs = (_lib.vp * nsrc)(*[s.data_ptr() for s in sources])
+    desc_d = torch.from_numpy(desc).to(out.device)
+    ctx = _stat_ctx(out)
+    check(ctx.lib.spyhip_concat(ctx.handle, out.element_size(), nsrc, ptrs, rows.ctypes.data_as(_lib.c_i64p),
+                                run.ctypes.data_as(_lib.c_i64p), int(pre), desc.ctypes.data_as(_lib.c_i64p), _ptr(desc_d),
+                                desc.shape[0], _ptr(out), int(out.shape[0])), "spyhip_concat")
+    return out
