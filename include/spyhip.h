@@ -667,6 +667,37 @@ int spyhip_concat(spyhip_ctx* ctx, int elem_bytes, int nsrc, const void* const* 
                   const int64_t* run, int64_t pre, const int64_t* desc, const int64_t* desc_d, int64_t ntrials,
                   void* out_d, int64_t out_rows);
 
+/* ---- synthetic data (synthdata.py; syncopy/synthdata/analog.py).  The deterministic part of a trial, assembled from
+ * random numbers that the HOST drew (there is no device random stream, so every result has a reference value for every
+ * seed).  Every tensor is (ntrials, nsamples, nchan), C-order.  Asynchronous on the context's stream; nothing is
+ * allocated, no atomics, no workgroup waits on another.
+ *
+ * spyhip_synth_ar2: the network of coupled AR(2) processes.  noise_d holds the float64 innovations; out[t][0] and
+ * out[t][1] are noise[t][0] and noise[t][1] rounded to float32, and for i >= 2
+ *     acc = sum_j M[c][j] * (double)out[t][i-1][j]      (float64, ascending j, fused multiply-adds)
+ *     v   = (float)(acc + (double)((float)alpha2 * out[t][i-2][c]))
+ *     out[t][i][c] = (float)((double)v + noise[t][i][c])
+ * with M = diag(alpha1) + AdjMat.T.  The coupling is the CSR table of the non-zeros of AdjMat.T: receiver c has the
+ * senders col[rowptr[c] .. rowptr[c + 1]), strictly ascending, with the float32 weights w; alpha1 joins the sum at j = c
+ * (added to the table's weight in float64 where the table has a diagonal entry).  rowptr and col are the host copies,
+ * which are checked before anything runs, rowptr_d, col_d and w_d the table on the device (col, col_d and w_d may be
+ * NULL for an empty table).  -1 for fewer than 2 samples, nchan outside 1 .. 1024, a tensor too large for 64-bit
+ * offsets and a malformed table.  With an entry off the diagonal one workgroup walks a trial, one thread per channel,
+ * the table in LDS where it fits; without one, one thread walks each (trial, channel) series.
+ *
+ * spyhip_synth_phase: phase diffusion.  wn_d is float32 white noise, lin_d (nsamples) the linear phase, ps0_d (ntrials, nchan)
+ * the initial phases: phase[t][i][c] = (lin[i] + ps0[t][c]) + S[t][i][c], S the running float32 sum of (float)rel_eps * wn in
+ * sample order (np.cumsum's); out is the phase, or cosf(phase) where want_cos is set.  All float32, single operations.
+ *
+ * spyhip_synth_tile: out[t][i][c] = col_d[i] (nsamples float32 values), in 16-byte lanes where nchan is a multiple of 4
+ * and out_d lies on a 16-byte boundary. */
+int spyhip_synth_ar2(spyhip_ctx* ctx, const double* noise_d, int64_t ntrials, int64_t nsamples, int nchan, double alpha1,
+                     double alpha2, const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_d,
+                     const int32_t* col_d, const float* w_d, float* out_d);
+int spyhip_synth_phase(spyhip_ctx* ctx, const float* wn_d, const float* lin_d, const float* ps0_d, double rel_eps,
+                       int64_t ntrials, int64_t nsamples, int nchan, int want_cos, float* out_d);
+int spyhip_synth_tile(spyhip_ctx* ctx, const float* col_d, int64_t ntrials, int64_t nsamples, int nchan, float* out_d);
+
 #ifdef __cplusplus
 }
 #endif

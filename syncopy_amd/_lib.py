@@ -129,6 +129,10 @@ SIGNATURES = {
                                 C.c_int64, vp, C.c_int64]),
     "spyhip_concat": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp), c_i64p, c_i64p, C.c_int64, c_i64p, vp, C.c_int64,
                                 vp, C.c_int64]),
+    "spyhip_synth_ar2": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, c_i32p, c_i32p, vp, vp,
+                                   vp, vp]),
+    "spyhip_synth_phase": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_int, vp]),
+    "spyhip_synth_tile": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int, vp]),
 }
 
 

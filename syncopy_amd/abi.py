@@ -454,6 +454,65 @@ class Device:
             for b in bufs:
                 b.free()
 
+    # ---- synthetic data: the deterministic part of a trial, from noise the host drew
+    def _synth(self, bufs, out, call, name):
+        try:
+            check(call(out.ptr), name)
+            return out.numpy()
+        finally:
+            self.synchronize()
+            for b in bufs + [out]:
+                b.free()
+
+    def synth_ar2(self, noise, AdjMat, alphas=(0.55, -0.8)):
+        """The AR(2) network of synthdata.ar2_network driven by `noise` ((ntrials, nsamples, nchan) float64 innovations
+        whose first two samples are the initial values): (ntrials, nsamples, nchan) float32.  See spyhip_synth_ar2 in
+        include/spyhip.h."""
+        from .synthdata import coupling_table
+        noise = np.ascontiguousarray(noise, dtype=np.float64)
+        if noise.ndim != 3:
+            raise ValueError("noise must be (ntrials, nsamples, nchan)")
+        rowptr, col, w = coupling_table(AdjMat)
+        if rowptr.size != noise.shape[2] + 1:
+            raise ValueError("AdjMat must be (nchan, nchan)")
+        if noise.shape[0] == 0:
+            return np.empty(noise.shape, dtype=np.float32)
+        bufs = [self._put(noise, np.float64), self._put(rowptr, np.int32)]
+        if col.size:
+            bufs += [self._put(col, np.int32), self._put(w, np.float32)]
+        col_d, w_d = (bufs[2].ptr, bufs[3].ptr) if col.size else (None, None)
+        T, n, c = noise.shape
+        return self._synth(bufs, Buffer(self, noise.shape, np.float32), lambda out: self.lib.spyhip_synth_ar2(
+            self.handle, bufs[0].ptr, T, n, c, float(alphas[0]), float(alphas[1]), rowptr.ctypes.data_as(_lib.c_i32p),
+            col.ctypes.data_as(_lib.c_i32p), bufs[1].ptr, col_d, w_d, out), "spyhip_synth_ar2")
+
+    def synth_phase(self, wn, lin, ps0, rel_eps, want_cos=True):
+        """(lin[i] + ps0[t][c]) + cumsum((float)rel_eps * wn) along the samples, or its cosine, float32.  wn: (ntrials,
+        nsamples, nchan); lin: (nsamples); ps0: (ntrials, nchan).  See spyhip_synth_phase in include/spyhip.h."""
+        wn = np.ascontiguousarray(wn, dtype=np.float32)
+        if wn.ndim != 3:
+            raise ValueError("wn must be (ntrials, nsamples, nchan)")
+        T, n, c = wn.shape
+        lin, ps0 = np.ascontiguousarray(lin, dtype=np.float32), np.ascontiguousarray(ps0, dtype=np.float32)
+        if lin.shape != (n,) or ps0.shape != (T, c):
+            raise ValueError("lin must be (nsamples) and ps0 (ntrials, nchan)")
+        if wn.size == 0:
+            return np.empty(wn.shape, dtype=np.float32)
+        bufs = [self._put(wn, np.float32), self._put(lin, np.float32), self._put(ps0, np.float32)]
+        return self._synth(bufs, Buffer(self, wn.shape, np.float32), lambda out: self.lib.spyhip_synth_phase(
+            self.handle, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, float(rel_eps), T, n, c, int(bool(want_cos)), out),
+            "spyhip_synth_phase")
+
+    def synth_tile(self, col, ntrials, nchan):
+        """out[t][i][c] = col[i]: (ntrials, len(col), nchan) float32.  See spyhip_synth_tile in include/spyhip.h."""
+        col = np.ascontiguousarray(col, dtype=np.float32).reshape(-1)
+        shape = (int(ntrials), col.size, int(nchan))
+        if int(np.prod(shape)) == 0:
+            return np.empty(shape, dtype=np.float32)
+        bufs = [self._put(col, np.float32)]
+        return self._synth(bufs, Buffer(self, shape, np.float32), lambda out: self.lib.spyhip_synth_tile(
+            self.handle, bufs[0].ptr, shape[0], shape[1], shape[2], out), "spyhip_synth_tile")
+
     def close(self):
         if self.handle is not None:
             self.lib.spyhip_ctx_destroy(self.handle)

@@ -1555,3 +1555,52 @@ def concat(sources, desc, out, pre=1):
                                 run.ctypes.data_as(_lib.c_i64p), int(pre), desc.ctypes.data_as(_lib.c_i64p), _ptr(desc_d),
                                 desc.shape[0], _ptr(out), int(out.shape[0])), "spyhip_concat")
     return out
+
+
+# ---- synthetic data (csrc/synth.hip) -----------------------------------------------------------------------------------
+def synth_table(rowptr, col, w, device):
+    """the coupling table of synthdata.coupling_table with its copy on `device`, for synth_ar2"""
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+    col, w = np.ascontiguousarray(col, dtype=np.int32), np.ascontiguousarray(w, dtype=np.float32)
+    return rowptr, col, torch.from_numpy(rowptr).to(device), torch.from_numpy(col).to(device), torch.from_numpy(w).to(device)
+
+
+def synth_ar2(noise, alpha1, alpha2, table, out):
+    """out = the AR(2) network driven by `noise` ((ntrials, nsamples, nchan) float64 innovations, whose first two samples
+    are the initial values), one launch; out: float32, contiguous, ntrials * nsamples rows of nchan channels.  table:
+    synth_table's.  See include/spyhip.h: spyhip_synth_ar2."""
+    assert noise.is_cuda and noise.dtype == torch.float64 and noise.is_contiguous() and noise.dim() == 3
+    T, n, c = (int(s) for s in noise.shape)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == noise.numel()
+    rowptr, col, rowptr_d, col_d, w_d = table
+    assert rowptr.size == c + 1 and rowptr_d.device == noise.device == out.device
+    ctx = _stat_ctx(out)
+    check(ctx.lib.spyhip_synth_ar2(ctx.handle, _ptr(noise), T, n, c, float(alpha1), float(alpha2),
+                                   rowptr.ctypes.data_as(_lib.c_i32p), col.ctypes.data_as(_lib.c_i32p), _ptr(rowptr_d),
+                                   _ptr(col_d), _ptr(w_d), _ptr(out)), "spyhip_synth_ar2")
+    return out
+
+
+def synth_phase(wn, lin, ps0, rel_eps, want_cos, out):
+    """out = the phase (lin[i] + ps0[t][c]) + cumsum((float)rel_eps * wn) along the samples, or its cosine, one launch.
+    wn: (ntrials, nsamples, nchan) float32; lin: (nsamples) float32; ps0: (ntrials, nchan) float32; out like synth_ar2's."""
+    assert wn.is_cuda and wn.dtype == torch.float32 and wn.is_contiguous() and wn.dim() == 3
+    T, n, c = (int(s) for s in wn.shape)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == wn.numel()
+    assert lin.is_cuda and lin.dtype == torch.float32 and lin.is_contiguous() and lin.numel() == n
+    assert ps0.is_cuda and ps0.dtype == torch.float32 and ps0.is_contiguous() and tuple(ps0.shape) == (T, c)
+    ctx = _stat_ctx(out)
+    check(ctx.lib.spyhip_synth_phase(ctx.handle, _ptr(wn), _ptr(lin), _ptr(ps0), float(rel_eps), T, n, c,
+                                     int(bool(want_cos)), _ptr(out)), "spyhip_synth_phase")
+    return out
+
+
+def synth_tile(col, ntrials, out):
+    """out[t][i][c] = col[i]: out float32, contiguous, (ntrials * len(col), nchan); one launch."""
+    assert col.is_cuda and col.dtype == torch.float32 and col.is_contiguous() and col.dim() == 1
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 2
+    assert out.shape[0] == int(ntrials) * col.numel() and out.device == col.device
+    ctx = _stat_ctx(out)
+    check(ctx.lib.spyhip_synth_tile(ctx.handle, _ptr(col), int(ntrials), int(col.numel()), int(out.shape[1]), _ptr(out)),
+          "spyhip_synth_tile")
+    return out
