@@ -298,6 +298,30 @@ int spyhip_ppc_accumulate_csd(spyhip_ctx* ctx, const void* csd_d, int ntrials, i
 int spyhip_ppc_finalize(spyhip_ctx* ctx, const void* acc_d, int nfreq, int ni, int nj, int lower_only,
                         int64_t ntrials, void* out_d);
 
+/* ---- K10: phase-lag index, weighted phase-lag index, phase-locking value ------
+ * Not in the reference (Stam 2007; Vinck 2011).  With S_t as for K7 and s_t = Im S_t (a positive scale changes nothing):
+ *   A = sum_t s_t,  B = sum_t |s_t|,  Q = sum_t s_t^2,  N = sum_t sign(s_t)   (sign(0) = 0),
+ *   pli = |N| / T,  wpli = |A| / B (0 where B = 0),  wpli_debiased = (A^2 - Q) / (B^2 - Q) (0 where B^2 - Q <= 0),
+ *   plv = |sum_t u_t| / T  with K7's unit phasors.
+ * spyhip_phaselag_accumulate: acc[f,i,j] += {A, B, Q, N} of the batch straight from the tapered spectra (spec_d as for
+ *   spyhip_ppc_accumulate); acc_d float32 (nfreq, nchan, nchan, 4), zeroed by the caller, maintained on the lower
+ *   triangle (32x32 tile granularity); plain sums, so ranks are combined by one sum.  -3: the tapers do not fit the LDS.
+ * spyhip_phaselag_accumulate_csd: the same sums from single-trial cross spectra that exist already
+ *   (csd_d complex64 (ntrials, nelem), acc_d float32 (nelem, 4)).
+ * spyhip_phaselag_finalize: out float32 (nfreq, ni, nj) for one `measure` from the accumulator and the total number of
+ *   trials (at least 2), evaluated in float64; lower_only = 1 for accumulators of spyhip_phaselag_accumulate: the upper
+ *   triangle is mirrored and the diagonal is exactly 0.  Without it the rectangle is evaluated element by element.
+ * spyhip_plv_finalize: out float32 (nfreq, ni, nj) = |U| / ntrials from an accumulator of spyhip_ppc_accumulate
+ *   (lower_only = 1) or spyhip_ppc_accumulate_csd. */
+enum { SPYHIP_PHASELAG_PLI = 0, SPYHIP_PHASELAG_WPLI = 1, SPYHIP_PHASELAG_WPLI_DEBIASED = 2 };
+int spyhip_phaselag_accumulate(spyhip_ctx* ctx, const void* spec_d, int ntrials, int ntaper, int nfreq, int nchan,
+                               void* acc_d);
+int spyhip_phaselag_accumulate_csd(spyhip_ctx* ctx, const void* csd_d, int ntrials, int64_t nelem, void* acc_d);
+int spyhip_phaselag_finalize(spyhip_ctx* ctx, const void* acc_d, int nfreq, int ni, int nj, int lower_only,
+                             int64_t ntrials, int measure, void* out_d);
+int spyhip_plv_finalize(spyhip_ctx* ctx, const void* acc_d, int nfreq, int ni, int nj, int lower_only,
+                        int64_t ntrials, void* out_d);
+
 /* ---- K9: streaming jackknife of the coherence --------------------------------
  * Replaces, for method='coh' with jackknife=True, the T leave-one-out trial averages (statistics/jackknifing.py:14-108),
  * the AV stage on every replicate (connectivity_analysis.py:736-745) and the sums behind bias_var (:111-184):

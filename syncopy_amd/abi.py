@@ -29,6 +29,7 @@ from ._lib import SpyHipError, check  # noqa: F401
 OUTPUT_KIND = {"pow": 0, "abs": 1, "fourier": 2, "complex": 2, "real": 3, "imag": 4, "angle": 5,
                "absreal": 6, "absimag": 7}
 DETREND = {None: -1, False: -1, 0: 0, 1: 1}
+PHASELAG_MEASURE = {"pli": 0, "wpli": 1, "wpli_debiased": 2}       # SPYHIP_PHASELAG_* (include/spyhip.h)
 
 
 class Buffer:
@@ -206,6 +207,36 @@ class Device:
         out = Buffer(self, (F, Cn, Cn), np.complex64 if kind == 2 else np.float32)
         check(self.lib.spyhip_coh_from_accumulator(self.handle, acc.ptr, F, Cn, 1.0 / (K * T), kind, out.ptr),
               "spyhip_coh_from_accumulator")
+        res = out.numpy()
+        out.free()
+        acc.free()
+        return res
+
+    # ---- K1 + K7 / K10
+    def phase_measure(self, queue, tapers, scale, nfft=None, detrend=0, method="wpli", ntrials_total=None):
+        """connectivityanalysis(method='ppc' | 'plv' | 'pli' | 'wpli' | 'wpli_debiased'): (F, C, C) float32.  The sums
+        over this rank's trials are summed over ranks if a communicator exists (`ntrials_total`: all ranks' trials)."""
+        if method not in ("ppc", "plv") + tuple(PHASELAG_MEASURE):
+            raise ValueError(f"no phase measure {method!r}")
+        spec = self.mtmfft(queue, tapers, scale, nfft, detrend, False, None, "fourier", True, device_result=True)
+        T, K, F, Cn = spec.shape
+        phasors = method in ("ppc", "plv")
+        acc = Buffer(self, (F, Cn, Cn, 2 if phasors else 4), np.float32, zero=True)
+        accumulate = self.lib.spyhip_ppc_accumulate if phasors else self.lib.spyhip_phaselag_accumulate
+        check(accumulate(self.handle, spec.ptr, T, K, F, Cn, acc.ptr), "spyhip_%s_accumulate" % ("ppc" if phasors else "phaselag"))
+        self.synchronize()
+        spec.free()
+        if self.has_comm:
+            check(self.lib.spyhip_allreduce(self.handle, acc.ptr, int(np.prod(acc.shape)), 0), "spyhip_allreduce")
+        T = T if ntrials_total is None else int(ntrials_total)
+        out = Buffer(self, (F, Cn, Cn), np.float32)
+        if method == "ppc":
+            check(self.lib.spyhip_ppc_finalize(self.handle, acc.ptr, F, Cn, Cn, 1, T, out.ptr), "spyhip_ppc_finalize")
+        elif method == "plv":
+            check(self.lib.spyhip_plv_finalize(self.handle, acc.ptr, F, Cn, Cn, 1, T, out.ptr), "spyhip_plv_finalize")
+        else:
+            check(self.lib.spyhip_phaselag_finalize(self.handle, acc.ptr, F, Cn, Cn, 1, T, PHASELAG_MEASURE[method], out.ptr),
+                  "spyhip_phaselag_finalize")
         res = out.numpy()
         out.free()
         acc.free()

@@ -971,6 +971,72 @@ def ppc_finalize(acc, ntrials, lower_only):
     return out
 
 
+PHASELAG_MEASURE = {"pli": 0, "wpli": 1, "wpli_debiased": 2}       # SPYHIP_PHASELAG_* (include/spyhip.h)
+
+
+def phaselag_accumulate(spec, ntaper, acc):
+    """acc (F, C, C, 4) float32 += the sums {A, B, Q, N} over trials of the imaginary parts of the single-trial cross
+    spectra, straight from tapered spectra spec (ntrials * ntaper, F, C) complex64 (K10; lower triangle maintained)."""
+    assert spec.is_cuda and spec.dtype == torch.complex64 and spec.is_contiguous() and spec.dim() == 3
+    assert acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous()
+    R, F, Cn = spec.shape
+    assert R % ntaper == 0 and tuple(acc.shape) == (F, Cn, Cn, 4)
+    ctx = context(spec.device)
+    ctx.bind_stream()
+    check(ctx.lib.spyhip_phaselag_accumulate(ctx.handle, _ptr(spec), R // ntaper, int(ntaper), F, Cn, _ptr(acc)),
+          "spyhip_phaselag_accumulate")
+
+
+def phaselag_accumulate_csd(csd, acc):
+    """acc (..., 4) float32 += {A, B, Q, N} of the single-trial cross spectra csd (ntrials, ...) complex64."""
+    assert csd.is_cuda and csd.dtype == torch.complex64 and csd.is_contiguous()
+    assert acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous()
+    assert tuple(acc.shape) == tuple(csd.shape[1:]) + (4,)
+    ctx = context(csd.device)
+    ctx.bind_stream()
+    check(ctx.lib.spyhip_phaselag_accumulate_csd(ctx.handle, _ptr(csd), csd.shape[0], acc.numel() // 4, _ptr(acc)),
+          "spyhip_phaselag_accumulate_csd")
+
+
+def phaselag_finalize(acc, ntrials, lower_only, measure):
+    """'pli' | 'wpli' | 'wpli_debiased' (F, ni, nj) float32 from the accumulated sums (F, ni, nj, 4) of `ntrials` trials."""
+    assert acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous() and acc.dim() == 4 and acc.shape[3] == 4
+    F, ni, nj, _ = acc.shape
+    out = torch.empty((F, ni, nj), dtype=torch.float32, device=acc.device)
+    ctx = context(acc.device)
+    ctx.bind_stream()
+    check(ctx.lib.spyhip_phaselag_finalize(ctx.handle, _ptr(acc), F, ni, nj, int(bool(lower_only)), int(ntrials),
+                                           PHASELAG_MEASURE[measure], _ptr(out)), "spyhip_phaselag_finalize")
+    return out
+
+
+def plv_finalize(acc, ntrials, lower_only):
+    """Phase-locking value (F, ni, nj) float32 from K7's accumulated phasor sums of `ntrials` trials."""
+    assert acc.is_cuda and acc.dtype == torch.complex64 and acc.is_contiguous() and acc.dim() == 3
+    F, ni, nj = acc.shape
+    out = torch.empty((F, ni, nj), dtype=torch.float32, device=acc.device)
+    ctx = context(acc.device)
+    ctx.bind_stream()
+    check(ctx.lib.spyhip_plv_finalize(ctx.handle, _ptr(acc), F, ni, nj, int(bool(lower_only)), int(ntrials),
+                                      _ptr(out)), "spyhip_plv_finalize")
+    return out
+
+
+def phase_accumulator(method, shape, device):
+    """the zeroed accumulator of a phase measure over `shape` = (F, ni, nj), how to add a batch of tapered spectra or of
+    single-trial cross spectra to it, and how to finish it: K7's phasor sums for 'ppc' and 'plv', K10's four sums for
+    'pli', 'wpli' and 'wpli_debiased'.  Returns (acc, accumulate(spec, ntaper, acc), accumulate_csd(csd, acc),
+    finalize(acc, ntrials, lower_only))."""
+    if method in ("ppc", "plv"):
+        acc = torch.zeros(tuple(shape), dtype=torch.complex64, device=device)
+        return acc, ppc_accumulate, ppc_accumulate_csd, ppc_finalize if method == "ppc" else plv_finalize
+    if method not in PHASELAG_MEASURE:
+        raise ValueError(f"no phase measure {method!r}")
+    acc = torch.zeros(tuple(shape) + (4,), dtype=torch.float32, device=device)
+    return (acc, phaselag_accumulate, phaselag_accumulate_csd,
+            lambda a, ntrials, lower_only: phaselag_finalize(a, ntrials, lower_only, method))
+
+
 def jack_coh_accumulate(spec, ntaper, csd, direct, output, ntrials_total, sum_d, sum_d2):
     """Streaming jackknife of the coherence (K9): for every trial of spec (ntrials * ntaper, F, C) the leave-one-out
     coherence replicate minus `direct` is summed into sum_d (float64 / complex128) and its squared modulus into

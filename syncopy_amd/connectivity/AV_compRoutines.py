@@ -37,6 +37,21 @@ def pairwise_phase_consistency(st_csd):
     return backend.to_host(backend.ppc_finalize(acc, T, lower_only=False))[np.newaxis]
 
 
+def phase_lag(st_csd, measure):
+    """'plv' | 'pli' | 'wpli' | 'wpli_debiased' of kept single-trial cross spectra (T, F, Ni, Nj) complex64 ->
+    (1, F, Ni, Nj) float32 (not in the reference): the sums over trials of the batched path (backend.phase_accumulator),
+    taken element by element, then its finalizer on the rectangle."""
+    backend.require_gpu()
+    st_csd = np.asarray(st_csd)
+    T = st_csd.shape[0]
+    acc, _, accumulate_csd, finalize = backend.phase_accumulator(measure, st_csd.shape[1:], "cuda")
+    per = max(1, int((1 << 30) // max(1, int(np.prod(st_csd.shape[1:])) * 8)))
+    for t0 in range(0, T, per):
+        dev = torch.from_numpy(np.ascontiguousarray(st_csd[t0:t0 + per], dtype=np.complex64)).cuda()
+        accumulate_csd(dev, acc)
+    return backend.to_host(finalize(acc, T, lower_only=False))[np.newaxis]
+
+
 class _AverageRoutine(ComputationalRoutine):
     dimord = ["time", "freq", "channel_i", "channel_j"]
 

@@ -10,7 +10,7 @@ import torch
 from .. import backend, parallel
 from ..datatype import device_rows, selected_channels, trial_rows
 from ..shared.computational_routine import ComputationalRoutine, propagate_properties
-from ..shared.const_def import spectralDTypes
+from ..shared.const_def import phaseMethods, spectralDTypes
 from ..shared.errors import SPYValueError
 from ..shared.tools import best_match
 from ..specest import hip_spectral as hs
@@ -163,11 +163,13 @@ class SpectralDyadicProduct(ComputationalRoutine):
         out._dev = acc.reshape(self.outputShape)
         out.data = backend.to_host(out._dev)
 
-    def ppc_hip(self, data):
+    def ppc_hip(self, data, measure="ppc"):
         """Pairwise phase consistency of spectra that exist already: K7 on the uploaded (trials x tapers, F, C) block of
         every time sample (time-resolved spectra: all trials must have the same number of samples, as the reference's
         accumulator `st_out.trials[0].shape` requires, connectivity_analysis.py:626); `channelcmb` rectangles are
-        cut out of the channels that occur at all.  Returns (nTime, F, C_i, C_j) on the device."""
+        cut out of the channels that occur at all.  `measure`: 'ppc', or one of its siblings 'plv' (K7's sums, another
+        finalizer), 'pli', 'wpli', 'wpli_debiased' (K10: backend.phase_accumulator).  Returns (nTime, F, C_i, C_j) on the
+        device."""
         rows, chans = trial_rows(data), selected_channels(data)
         T = self.numTrials
         lens = {rows[k][1] - rows[k][0] for k in range(T)}
@@ -186,12 +188,12 @@ class SpectralDyadicProduct(ComputationalRoutine):
         first = np.array([rows[k][0] for k in mine], dtype=np.int64)
         res = []
         for ti in range(L):
-            U = torch.zeros((F, C, C), dtype=torch.complex64, device="cuda")
+            U, accumulate, _, finalize = backend.phase_accumulator(measure, (F, C, C), "cuda")
             if len(mine):
                 dev = torch.from_numpy(np.ascontiguousarray(host[first + ti], dtype=np.complex64)).cuda()
-                backend.ppc_accumulate(dev.reshape(-1, F, C), K, U)
+                accumulate(dev.reshape(-1, F, C), K, U)
             parallel.allreduce_sum_(U)
-            r = backend.ppc_finalize(U, T, lower_only=True)
+            r = finalize(U, T, lower_only=True)
             res.append(r if sub is None else _cmb_block(r, sub))
         return torch.stack(res, dim=0)
 
@@ -290,7 +292,7 @@ class CrossSpectra(ComputationalRoutine):
         nS = cfg["nSamples"] if cfg["nSamples"] is not None else rows[0][1] - rows[0][0]
         _, freq_idx = _freq_selection(nS, cfg["samplerate"], cfg["foi"])
         T = len(rows)
-        if method == "ppc" and T <= 16:
+        if method in phaseMethods and T <= 16:
             # every trial's unit phasor weighs 2 / T >= 1 / 8 of the estimate: where a single-trial cross spectrum passes
             # near zero its phase is the transform's rounding noise (5e-7 of the spectrum in float32, 6e-8 in the reference's
             # complex64 products of float64 transforms) and nothing averages it away - 1.49 x the criterion for one of
@@ -320,16 +322,17 @@ class CrossSpectra(ComputationalRoutine):
         ratio = parallel.allreduce_max(ratio)
         # (7.5e-7, not the 5e-7 of the estimate above: two of 48000 seeded cases sat at 1.2 x and 1.5 x the criterion with float32
         # transforms the plain estimate had let through - profiles/r4_fuzz_offset1300000.log)
-        if method == "ppc":
+        if method in phaseMethods:
             return bool(7.5e-7 * np.sqrt(ratio) * 2 / T > 5e-6 / np.sqrt(max(T, 1)))
         return bool(7.5e-7 * np.sqrt(ratio / (T * K)) > 1e-6)
 
-    def ppc_hip(self, data):
+    def ppc_hip(self, data, measure="ppc"):
         """Pairwise phase consistency with the kernels (connectivity_analysis.py:624-663, ST_compRoutines.py:159-233):
         the tapered spectra of each batch of trials go straight into K7, which forms every trial's taper-averaged
         cross spectrum, normalises it to a unit phasor and sums over trials in registers; one sum over ranks, then
         ppc = (|U|^2 - T)/(T(T-1)).  No single-trial cross spectrum is ever stored (the reference keeps all T of them
-        and visits T(T-1)/2 pairs).  Returns the (F, C, C) float32 device tensor."""
+        and visits T(T-1)/2 pairs).  `measure`: 'ppc', or one of its siblings 'plv' (the same sums, |U| / T), 'pli', 'wpli',
+        'wpli_debiased' (K10 on the same stream: backend.phase_accumulator).  Returns the (F, C, C) float32 device tensor."""
         cfg = self.cfg
         dev = data.device_data()
         rows, chans = device_rows(data), selected_channels(data)
@@ -339,13 +342,13 @@ class CrossSpectra(ComputationalRoutine):
         F, C = self.targetShapes[0][1], self.targetShapes[0][2]
         T = self.numTrials
         mine = [rows[k] for k in self.my_trials()]
-        U = torch.zeros((F, C, C), dtype=torch.complex64, device=dev.device)
+        U, accumulate, _, finalize = backend.phase_accumulator(measure, (F, C, C), dev.device)
         for _, spec in hs.run_mtmfft_batches(dev, mine, chans, cfg["nSamples"], cfg["taper"], cfg["taper_opt"],
                                              cfg["demean_taper"], False, pr, freq_idx, "fourier", True, reuse=True):
-            backend.ppc_accumulate(spec.reshape(-1, F, C), spec.shape[1], U)
+            accumulate(spec.reshape(-1, F, C), spec.shape[1], U)
         parallel.allreduce_sum_(U)
         self.metadata = [{"freqs_hash": _freqs_hash(freqs)}] * T
-        return backend.ppc_finalize(U, T, lower_only=True)
+        return finalize(U, T, lower_only=True)
 
     def jackknife_hip(self, data, evaluate, fused=None):
         """Streaming jackknife on the device (connectivity_analysis.py:601-606,736-757; statistics/jackknifing.py):

@@ -1,10 +1,12 @@
-"""`connectivityanalysis` metafunction: method = 'csd' | 'coh' | 'granger' | 'ppc' | 'corr'.
+"""`connectivityanalysis` metafunction: method = 'csd' | 'coh' | 'granger' | 'ppc' | 'corr', and beyond the reference
+'plv' | 'pli' | 'wpli' | 'wpli_debiased', which behave as 'ppc' does throughout.
 
 Two-stage pipeline of syncopy/connectivity/connectivity_analysis.py: single-trial
 cross-spectra accumulated over trials (ST stage, :587-599), then one evaluation on the
 trial average (AV stage, :677-679).  Parameter handling follows :286-473 and the
 `cross_spectra` helper (:775-872).
 """
+import functools
 import numbers
 import weakref
 
@@ -12,12 +14,12 @@ import numpy as np
 
 from ..datatype import (AnalogData, CrossSpectralData, SpectralData, require_real_analog, selected_channels,
                         selected_trialdefinition)
-from ..shared.const_def import connectivity_outputs, connectivityMethods
+from ..shared.const_def import connectivity_outputs, connectivityMethods, phaseMethods
 from ..shared.errors import SPYTypeError, SPYValueError, SPYWarning
 from ..shared.kwarg_decorators import attached_selection, unwrap_cfg
 from ..shared.input_processors import process_foi, process_padding, process_taper
 from ..shared.tools import best_match
-from .AV_compRoutines import NormalizeCrossCov, NormalizeCrossSpectra, pairwise_phase_consistency
+from .AV_compRoutines import NormalizeCrossCov, NormalizeCrossSpectra, pairwise_phase_consistency, phase_lag
 from .ST_compRoutines import CrossCovariance, CrossSpectra, SpectralDyadicProduct
 
 
@@ -56,6 +58,7 @@ def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi
             raise SPYValueError("0, 1 or None", varname="polyremoval", actual=polyremoval)
     classes = {"csd": CrossSpectra, "coh": NormalizeCrossSpectra, "dyadic": SpectralDyadicProduct,
                "ppc": pairwise_phase_consistency, "ccov": CrossCovariance, "ccov_norm": NormalizeCrossCov}
+    classes.update({m: functools.partial(phase_lag, measure=m) for m in phaseMethods if m != "ppc"})
     try:
         from .AV_compRoutines import GrangerCausality
         classes["granger"] = GrangerCausality
@@ -178,7 +181,7 @@ def _connectivity_from_spectra(data, classes, method, keeptrials, output, comput
     if method == "granger" and data.data.shape[data.dimord.index("time")] != len(data.sampleinfo):
         raise NotImplementedError("Time resolved Granger causality from tf-spectra not available atm")
     log_dict = {"method": method, "output": output, "keeptrials": keeptrials}
-    if cmb is not None and method in ("csd", "ppc"):
+    if cmb is not None and (method == "csd" or method in phaseMethods):
         # truly rectangular products (connectivity_analysis.py:503-529)
         st = classes["dyadic"](send_idx=cmb[0], send_N=len(cmb[0]), rec_idx=cmb[1], rec_N=len(cmb[1]))
     else:
@@ -235,7 +238,7 @@ def _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, p
     if nTrials == 1 and method != "corr":
         raise SPYValueError("multi-trial input data, spectral connectivity measures critically depend on trial "
                             "averaging!", "data", "only one trial")
-    if keeptrials is not False and method in ("coh", "ppc", "granger"):
+    if keeptrials is not False and method in ("coh", "granger") + phaseMethods:
         raise SPYValueError(f"False, trial averaging needed for method {method}!", varname="keeptrials",
                             actual=keeptrials)
     if method == "corr":
@@ -292,15 +295,17 @@ def _jackknife_on_device(data, st, av, st_out, log_dict):
     return out
 
 
-def _ppc(data, classes, st, compute_method, log_dict):
+def _ppc(data, classes, st, compute_method, log_dict, method="ppc"):
     """Pairwise phase consistency (connectivity_analysis.py:551-562,590,624-663): all trial pairs of the single-trial
     cross spectra.  With the kernels nothing is kept (K7 streams the trials); the per-trial engine path keeps the
-    single-trial cross spectra as the reference does and hands them to classes["ppc"]."""
+    single-trial cross spectra as the reference does and hands them to classes["ppc"].  `method`: 'ppc' or one of its
+    siblings (phaseMethods), which take the same two paths with their own sums (K10) and classes[method]."""
     from .. import backend
     out = CrossSpectralData(dimord=CrossSpectra.dimord)
     if compute_method in (None, "hip") and hasattr(st, "ppc_hip"):
         st.initialize(data, out._stackingDim, chan_per_worker=None, keeptrials=False)
-        res = st.ppc_hip(data)                       # (F, Ci, Cj) from raw trials, (nTime, F, Ci, Cj) from spectra
+        # (F, Ci, Cj) from raw trials, (nTime, F, Ci, Cj) from spectra
+        res = st.ppc_hip(data) if method == "ppc" else st.ppc_hip(data, measure=method)
         out._dev = res if res.dim() == 4 else res.unsqueeze(0)
         out.data = backend.to_host(out._dev)
         st.process_metadata(data, out)
@@ -315,8 +320,12 @@ def _ppc(data, classes, st, compute_method, log_dict):
                                 actual=f"time-resolved spectra with {sorted(lens)} samples per trial")
         L = lens.pop()
         per_time = single.reshape((-1, L) + single.shape[1:])            # (trials, time, F, C_i, C_j)
-        out.data = np.ascontiguousarray(np.concatenate([classes["ppc"](per_time[:, ti]) for ti in range(L)], axis=0),
-                                        dtype=np.float32)
+        res = np.ascontiguousarray(np.concatenate([classes[method](per_time[:, ti]) for ti in range(L)], axis=0),
+                                   dtype=np.float32)
+        if method in ("pli", "wpli", "wpli_debiased"):
+            # sender = receiver: exactly 0, as the batched path's finalizer writes it (Im S_ii is a rounding residue at best)
+            res[..., np.asarray(st_out.channel_i)[:, None] == np.asarray(st_out.channel_j)[None, :]] = 0.0
+        out.data = res
         out.samplerate, out.freq = st_out.samplerate, st_out.freq
         out.channel_i, out.channel_j = st_out.channel_i, st_out.channel_j
         out.trialdefinition = st_out.trialdefinition[:1].copy() if L > 1 else np.array([[0, 1.0, 0]])
@@ -335,7 +344,8 @@ def _run_stages(data, classes, st, method, keeptrials, output, compute_method, j
         # precision="auto": float64 transforms when the OUTPUT isolates a part of the complex coherency (its imaginary or real
         # part, its phase: 1.5e-7 of the modulus is not small against a part that nearly vanishes - as freqanalysis decides for
         # its own outputs), or when the DATA ask for them (CrossSpectra.needs_float64)
-        if (batched and hs.requested_precision() is None and method in ("coh", "granger", "ppc") and isinstance(data, AnalogData)
+        if (batched and hs.requested_precision() is None and method in ("coh", "granger") + phaseMethods
+                and isinstance(data, AnalogData)
                 and ((method == "coh" and output in ("imag", "angle", "real"))
                      or (hasattr(st, "needs_float64") and st.needs_float64(data, method)))):
             stack.enter_context(hs.soft_reference())
@@ -346,8 +356,8 @@ def _run_stages(data, classes, st, method, keeptrials, output, compute_method, j
 
 
 def _run_stages_impl(data, classes, st, method, keeptrials, output, compute_method, jackknife, log_dict):
-    if method == "ppc":
-        return _ppc(data, classes, st, compute_method, log_dict)
+    if method in phaseMethods:
+        return _ppc(data, classes, st, compute_method, log_dict, method)
     if method == "coh":
         if output not in connectivity_outputs:
             raise SPYValueError(f"one of {sorted(connectivity_outputs)}", varname="output", actual=output)

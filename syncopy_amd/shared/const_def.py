@@ -10,5 +10,7 @@ spectralDTypes = {
 availableTapers = [w for w in windows.__all__ if w not in ("get_window", "exponential", "dpss")]
 availablePaddingOpt = ["maxperlen", "nextpow2"]
 availableMethods = ("mtmfft", "mtmconvol", "wavelet", "superlet", "welch")
-connectivityMethods = ("coh", "corr", "csd", "granger", "ppc")
+connectivityMethods = ("coh", "corr", "csd", "granger", "ppc", "plv", "pli", "wpli", "wpli_debiased")
+# ppc and its siblings beyond the reference: non-linear in the single-trial cross spectrum, accumulated over trials
+phaseMethods = ("ppc", "plv", "pli", "wpli", "wpli_debiased")
 connectivity_outputs = {"abs", "pow", "complex", "fourier", "angle", "real", "imag"}
