@@ -450,6 +450,23 @@ int spyhip_wilson_finish(spyhip_ctx* ctx, const void* A_d, const void* psi_d, co
  * wilson_sf.py:77-109); for benchmarks and diagnostics. */
 int spyhip_granger_last_iterations(const spyhip_ctx* ctx);
 
+/* ---- K11: directed transfer function and partial directed coherence from the factors of K6 (not in the reference) ----
+ * spyhip_zinv: dst[b] = src[b]^-1 for `batch` complex128 n x n matrices on the device; dst_d may equal src_d.  The block
+ *   Gauss-Jordan kernel of the size class runs first (K6's inverse of the iteration, csrc/granger_route.h); if a matrix
+ *   flags a tiny pivot the whole batch is repeated with the partially pivoted kernel.  The flags (and, in place, a copy
+ *   of the input) live in the context's work arrays: nothing is allocated per call once they are large enough.
+ *   Return -7: a matrix is singular (a zero pivot under partial pivoting); dst is undefined then.
+ * spyhip_directed_norm: M_d complex128 (nfreq, n, n), w_d n doubles on the device or NULL (all ones), out_d float32
+ *   (nfreq, n, n) in the layout [f, sender, receiver] - the transpose of M's index order:
+ *     axis 0 (DTF, M = H):     out[f,s,r] = w_s |M[f,r,s]| / sqrt(sum_k w_k^2 |M[f,r,k]|^2)
+ *     axis 1 (PDC, M = H^-1):  out[f,s,r] = w_r |M[f,r,s]| / sqrt(sum_k w_k^2 |M[f,k,s]|^2)
+ *   squared = 1: the square.  A zero norm gives 0.  float64 arithmetic, one rounding to float32.  w = sqrt(diag Sigma)
+ *   with axis 0 is the directed coherence, w = 1 / sqrt(diag Sigma) with axis 1 the generalised PDC.  out_d must not be
+ *   M_d.  -3 if no tile fits the LDS of a workgroup (csrc/directed_route.h). */
+int spyhip_zinv(spyhip_ctx* ctx, const void* src_d, void* dst_d, int batch, int n);
+int spyhip_directed_norm(spyhip_ctx* ctx, const void* M_d, const void* w_d, int nfreq, int n, int axis, int squared,
+                         void* out_d);
+
 /* ---- utilities on the in-HBM trial queue ---------------------------------- */
 /* out[r, :] = alpha * sum_t in[t, r, :]  (trial mean of (T, n) float32) */
 int spyhip_trial_mean_f32(spyhip_ctx* ctx, const float* in_d, float* out_d, int64_t ntrials, int64_t n);

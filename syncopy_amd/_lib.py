@@ -90,6 +90,8 @@ SIGNATURES = {
     "spyhip_granger": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, vp, vp, vp,
                                  c_f64p]),
     "spyhip_granger_last_iterations": (C.c_int, [vp]),
+    "spyhip_zinv": (C.c_int, [vp, vp, vp, C.c_int, C.c_int]),
+    "spyhip_directed_norm": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "spyhip_wilson_cond": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, c_f64p]),
     "spyhip_wilson_init": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "spyhip_wilson_psi0": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),

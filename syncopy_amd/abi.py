@@ -242,6 +242,42 @@ class Device:
         acc.free()
         return res
 
+    # ---- directed measures of the Wilson factors
+    def zinv(self, M):
+        """np.linalg.inv of a stack of complex128 matrices (batch, n, n) with the Wilson stage's kernels (spyhip_zinv)."""
+        M = np.ascontiguousarray(M, dtype=np.complex128)
+        if M.ndim != 3 or M.shape[1] != M.shape[2]:
+            raise ValueError("M must be (batch, n, n)")
+        buf = self._put(M, np.complex128)
+        try:
+            check(self.lib.spyhip_zinv(self.handle, buf.ptr, buf.ptr, M.shape[0], M.shape[1]), "spyhip_zinv")
+            return buf.numpy()
+        finally:
+            self.synchronize()
+            buf.free()
+
+    def directed_norm(self, M, w=None, axis=0, squared=False):
+        """spyhip_directed_norm of complex128 `M` (F, n, n): float32 [f, sender, receiver], normalised along the rows
+        (axis 0: DTF of M = H) or the columns (axis 1: PDC of M = H^-1) of M with the weights `w` (n, or None)."""
+        M = np.ascontiguousarray(M, dtype=np.complex128)
+        if M.ndim != 3 or M.shape[1] != M.shape[2]:
+            raise ValueError("M must be (F, n, n)")
+        F, n, _ = M.shape
+        if w is not None and np.size(w) != n:
+            raise ValueError("w must hold one weight per channel")
+        md = self._put(M, np.complex128)
+        wd = self._put(np.ravel(w), np.float64) if w is not None else None
+        out = Buffer(self, (F, n, n), np.float32)
+        try:
+            check(self.lib.spyhip_directed_norm(self.handle, md.ptr, wd.ptr if wd is not None else None, F, n, int(axis),
+                                                int(bool(squared)), out.ptr), "spyhip_directed_norm")
+            return out.numpy()
+        finally:
+            self.synchronize()
+            for b in (md, wd, out):
+                if b is not None:
+                    b.free()
+
     # ---- spy.timelockanalysis
     def cov(self, trials, ddof=None):
         """np.cov(trial, ddof=ddof, rowvar=False) of every trial of `trials` (T, n, channels) float32: (T, channels,

@@ -1150,6 +1150,50 @@ def granger_stats(device=None):
     return {"iterations": int(ctx.lib.spyhip_granger_last_iterations(ctx.handle))}
 
 
+def zinv(M, out=None):
+    """Inverse of every matrix of a complex128 device tensor (batch, n, n) with the Wilson stage's kernels
+    (spyhip_zinv): into `out`, which may be `M` itself (in place); default: a new tensor.  A singular matrix raises."""
+    assert M.is_cuda and M.dtype == torch.complex128 and M.is_contiguous() and M.dim() == 3 and M.shape[1] == M.shape[2]
+    if out is None:
+        out = torch.empty_like(M)
+    assert out.is_cuda and out.dtype == torch.complex128 and out.is_contiguous() and out.shape == M.shape
+    ctx = context(M.device)
+    ctx.bind_stream()
+    check(ctx.lib.spyhip_zinv(ctx.handle, _ptr(M), _ptr(out), M.shape[0], M.shape[1]), "spyhip_zinv")
+    return out
+
+
+def directed_norm(M, w=None, axis=0, squared=False):
+    """Row- (axis 0, DTF) or column-normalised (axis 1, PDC) magnitudes of a complex128 device tensor (F, n, n) as float32
+    [f, sender, receiver] (spyhip_directed_norm); `w`: n float64 weights on the device or None."""
+    assert M.is_cuda and M.dtype == torch.complex128 and M.is_contiguous() and M.dim() == 3 and M.shape[1] == M.shape[2]
+    F, n, _ = M.shape
+    if w is not None:
+        assert w.is_cuda and w.dtype == torch.float64 and w.is_contiguous() and w.numel() == n
+    out = torch.empty((F, n, n), dtype=torch.float32, device=M.device)
+    ctx = context(M.device)
+    ctx.bind_stream()
+    check(ctx.lib.spyhip_directed_norm(ctx.handle, _ptr(M), _ptr(w), F, n, int(axis), int(bool(squared)), _ptr(out)),
+          "spyhip_directed_norm")
+    return out
+
+
+def directed(csd, method, noise_weighted=False, squared=False, rtol=5e-6, niter=100, cond_max=1e4, eps_max=1e-1):
+    """'dtf' | 'pdc' of a trial-averaged CSD (F, C, C) complex64 on the device: the Wilson factorisation of granger(),
+    then the normalisation of H (dtf) or of H^-1, inverted in place (pdc).  noise_weighted: directed coherence /
+    generalised PDC, weighted with sigma_k = sqrt(Re Sigma_kk).  Returns (float32 (F, C, C) [f, sender, receiver], info)."""
+    if method not in ("dtf", "pdc"):
+        raise ValueError(f"unknown directed measure {method!r}")
+    _, meta, H, Sig = granger(csd, rtol=rtol, niter=niter, cond_max=cond_max, eps_max=eps_max, want_factors=True)
+    w = None
+    if noise_weighted:
+        sigma = torch.sqrt(torch.diagonal(Sig).real)
+        w = (sigma if method == "dtf" else 1.0 / sigma).contiguous()
+    if method == "pdc":
+        zinv(H, out=H)
+    return directed_norm(H, w, axis=0 if method == "dtf" else 1, squared=squared), meta
+
+
 def axis_nanmean(x, axis):
     """np.nanmean(x, axis, keepdims=True) of one trial array (float32 / complex64) on the device, in NumPy's summation
     order (statistics/compRoutines.py:22-57)."""

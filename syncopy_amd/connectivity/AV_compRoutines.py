@@ -188,6 +188,53 @@ class GrangerCausality(_AverageRoutine):
             out.info[label] = bool(value) if cast == "bool" else float(value)
 
 
+def directed_cF(csd_av_dat, method="dtf", noise_weighted=False, output="abs", rtol=5e-6, nIter=100, cond_max=1e4,
+                chunkShape=None, noCompute=False):
+    """Directed transfer function ('dtf') or partial directed coherence ('pdc') from the trial-averaged CSD
+    (1, nFreq, N, N), not in the reference: the regularisation and Wilson factorisation of granger_cF, then
+    |H| normalised over the senders of a receiver (dtf) or |H^-1| over the receivers of a sender (pdc), weighted with
+    the noise variances for `noise_weighted` (directed coherence / generalised PDC); output 'pow' squares.  Returns
+    (1, nFreq, N, N) float32 [sender, receiver] and granger_cF's metadata keys."""
+    outShape = csd_av_dat.shape
+    if noCompute:
+        return outShape, spectralDTypes["abs"]
+    backend.require_gpu()
+    dev = torch.from_numpy(np.ascontiguousarray(csd_av_dat[0], dtype=np.complex64)).cuda()
+    res, meta = backend.directed(dev, method, noise_weighted=noise_weighted, squared=(output == "pow"), rtol=rtol,
+                                 niter=nIter, cond_max=cond_max, eps_max=1e-1)
+    return backend.to_host(res)[None, ...], _granger_metadata(meta)
+
+
+class DirectedMeasure(_AverageRoutine):
+    """AV stage of method 'dtf' / 'pdc'.  Every rank of a process group factorises the whole CSD it holds: the
+    frequency shards of GrangerCausality are not used here."""
+    computeFunction = staticmethod(directed_cF)
+    method = ""
+    valid_kws = ["method", "noise_weighted", "output", "rtol", "nIter", "cond_max"]
+    metadata_keys = GrangerCausality.metadata_keys
+
+    def process_metadata(self, data, out):
+        super().process_metadata(data, out)
+        for key, value in (self.metadata[0] or {}).items():
+            label, cast = key.split("--")
+            out.info[label] = bool(value) if cast == "bool" else float(value)
+
+    def _directed(self, csd):
+        cfg = self.cfg
+        return backend.directed(csd, cfg["method"], noise_weighted=cfg["noise_weighted"], squared=(cfg["output"] == "pow"),
+                                rtol=cfg["rtol"], niter=cfg["nIter"], cond_max=cfg["cond_max"], eps_max=1e-1)
+
+    def compute_hip(self, data, out):
+        dev = self._device_input(data)
+        res, self.metadata = [], []
+        for t in range(dev.shape[0]):
+            D, meta = self._directed(dev[t].contiguous())
+            res.append(D)
+            self.metadata.append(_granger_metadata(meta))
+        out._dev = torch.stack(res, dim=0)
+        out.data = backend.to_host(out._dev)
+
+
 def normalize_ccov_cF(trl_av_dat, chunkShape=None, noCompute=False):
     """Cross-correlation from the trial-averaged cross-covariance (nLags, 1, N, N): divided by the square roots of
     the zero-lag auto-covariances (AV_compRoutines.py:166-228)."""

@@ -1,5 +1,6 @@
 """`connectivityanalysis` metafunction: method = 'csd' | 'coh' | 'granger' | 'ppc' | 'corr', and beyond the reference
-'plv' | 'pli' | 'wpli' | 'wpli_debiased', which behave as 'ppc' does throughout.
+'plv' | 'pli' | 'wpli' | 'wpli_debiased', which behave as 'ppc' does throughout, and 'dtf' | 'pdc', which take every rule
+of 'granger' (they are measures of the same Wilson factors).
 
 Two-stage pipeline of syncopy/connectivity/connectivity_analysis.py: single-trial
 cross-spectra accumulated over trials (ST stage, :587-599), then one evaluation on the
@@ -14,7 +15,7 @@ import numpy as np
 
 from ..datatype import (AnalogData, CrossSpectralData, SpectralData, require_real_analog, selected_channels,
                         selected_trialdefinition)
-from ..shared.const_def import connectivity_outputs, connectivityMethods, phaseMethods
+from ..shared.const_def import connectivity_outputs, connectivityMethods, directedMethods, phaseMethods
 from ..shared.errors import SPYTypeError, SPYValueError, SPYWarning
 from ..shared.kwarg_decorators import attached_selection, unwrap_cfg
 from ..shared.input_processors import process_foi, process_padding, process_taper
@@ -27,7 +28,7 @@ from .ST_compRoutines import CrossCovariance, CrossSpectra, SpectralDyadicProduc
 def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi=None, foilim=None, pad="maxperlen",
                          polyremoval=0, tapsmofrq=None, nTaper=None, taper="hann", taper_opt=None, jackknife=False,
                          channelcmb=None, select=None, compute_method=None, routine_classes=None, precision="auto",
-                         **kwargs):
+                         noise_weighted=False, **kwargs):
     """Cross-spectral connectivity of AnalogData on MI355X (arguments as spy.connectivityanalysis,
     connectivity_analysis.py:51-67).
     `precision` (not a reference argument; as in `freqanalysis`): "reference" runs the taper product and the FFT of the
@@ -40,7 +41,12 @@ def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi
     the batched route transforms the first 16 trials in float32, looks at the dynamic range of their spectra
     (CrossSpectra.needs_float64: coh / granger / ppc) and runs the analysis with float64 transforms when the float32
     error in the result would pass its floor (the benchmark's AR(2) data never does; cost of the look: 16 trials'
-    transforms and one host synchronisation per call)."""
+    transforms and one host synchronisation per call).
+    `noise_weighted` (methods 'dtf' and 'pdc' only, which are not reference methods): weight the transfer function with
+    the noise variances of the factorisation - the directed coherence instead of the directed transfer function, the
+    generalised instead of the plain partial directed coherence.  Their `output` is 'abs' or 'pow' (the square, which
+    sums to 1 over the senders of a receiver for dtf, over the receivers of a sender for pdc); the result is laid out
+    [sender, receiver] as for 'granger', the diagonal included."""
     if precision not in ("float32", "reference", "auto"):
         raise SPYValueError("'float32', 'reference' or 'auto'", varname="precision", actual=str(precision))
     if not isinstance(data, (AnalogData, SpectralData)) or data.data is None:
@@ -53,6 +59,13 @@ def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi
     if jackknife and method not in ("coh", "granger"):
         SPYWarning(f"Jackknife is not available for method {method}")       # connectivity_analysis.py:310-317
         jackknife = False
+    if not isinstance(noise_weighted, bool):
+        raise SPYTypeError(noise_weighted, "noise_weighted", "boolean")
+    if noise_weighted and method not in directedMethods:
+        raise SPYValueError("False, noise weighting exists for the methods " + ", ".join(directedMethods) + " only",
+                            varname="noise_weighted", actual=f"True with method {method}")
+    if method in directedMethods and output not in ("abs", "pow"):
+        raise SPYValueError("'abs' or 'pow'", varname="output", actual=str(output))
     if polyremoval is not None:
         if not isinstance(polyremoval, numbers.Number) or polyremoval not in (0, 1):
             raise SPYValueError("0, 1 or None", varname="polyremoval", actual=polyremoval)
@@ -60,11 +73,15 @@ def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi
                "ppc": pairwise_phase_consistency, "ccov": CrossCovariance, "ccov_norm": NormalizeCrossCov}
     classes.update({m: functools.partial(phase_lag, measure=m) for m in phaseMethods if m != "ppc"})
     try:
-        from .AV_compRoutines import GrangerCausality
+        from .AV_compRoutines import DirectedMeasure, GrangerCausality
         classes["granger"] = GrangerCausality
+        classes.update({m: DirectedMeasure for m in directedMethods})
     except ImportError:
         pass
     classes.update(routine_classes or {})
+    for m in directedMethods:
+        if m in classes:
+            classes[m] = functools.partial(classes[m], method=m, noise_weighted=noise_weighted)
     with attached_selection(data, select):
         cmb = _parse_channelcmb(data, channelcmb)
         from ..specest import hip_spectral as hs
@@ -180,6 +197,8 @@ def _connectivity_from_spectra(data, classes, method, keeptrials, output, comput
                             "real valued spectral data")
     if method == "granger" and data.data.shape[data.dimord.index("time")] != len(data.sampleinfo):
         raise NotImplementedError("Time resolved Granger causality from tf-spectra not available atm")
+    if method in directedMethods and data.data.shape[data.dimord.index("time")] != len(data.sampleinfo):
+        raise NotImplementedError(f"Time resolved {method} from tf-spectra not available")
     log_dict = {"method": method, "output": output, "keeptrials": keeptrials}
     if cmb is not None and (method == "csd" or method in phaseMethods):
         # truly rectangular products (connectivity_analysis.py:503-529)
@@ -193,6 +212,11 @@ def _connectivity_from_spectra(data, classes, method, keeptrials, output, comput
             SPYWarning("jackknife estimates are not computed for pairwise (channelcmb) Granger causality")
         return _pairwise_granger(data, classes, st, compute_method, log_dict, *cmb)
     out = _run_stages(data, classes, st, method, keeptrials, output, compute_method, jackknife, log_dict)
+    if cmb is not None and method in directedMethods:
+        # the multivariate measure, post-selected: conditioning on every channel is the point of these measures
+        info = dict(out.info)
+        out = _post_select(out, *cmb)
+        out.info.update(info)
     if cmb is not None and method == "coh":
         jack = {k: getattr(out, k, None) for k in ("jack_var", "jack_bias")}
         out = _post_select(out, *cmb)
@@ -238,7 +262,7 @@ def _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, p
     if nTrials == 1 and method != "corr":
         raise SPYValueError("multi-trial input data, spectral connectivity measures critically depend on trial "
                             "averaging!", "data", "only one trial")
-    if keeptrials is not False and method in ("coh", "granger") + phaseMethods:
+    if keeptrials is not False and method in ("coh", "granger") + phaseMethods + directedMethods:
         raise SPYValueError(f"False, trial averaging needed for method {method}!", varname="keeptrials",
                             actual=keeptrials)
     if method == "corr":
@@ -247,7 +271,7 @@ def _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, p
         return _connectivity_from_spectra(data, classes, method, keeptrials, output, compute_method, jackknife, cmb)
     nSamples = process_padding(pad, lenTrials, fs)
     foi, foilim = process_foi(foi, foilim, fs)
-    if method == "granger":
+    if method == "granger" or method in directedMethods:
         if foi is not None or foilim is not None:
             raise SPYValueError("no foi specification for Granger analysis", "foi/foilim",
                                 "foi or foilim specification")
@@ -269,7 +293,7 @@ def _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, p
                 "pad": pad, "foi": foi, "taper": taper, "taper_opt": taper_opt}
 
     st = classes["csd"](samplerate=fs, nSamples=nSamples, taper=taper, taper_opt=taper_opt,
-                        demean_taper=(method == "granger"), polyremoval=polyremoval, timeAxis=timeAxis, foi=foi)
+                        demean_taper=(method == "granger" or method in directedMethods), polyremoval=polyremoval, timeAxis=timeAxis, foi=foi)
     return _run_stages(data, classes, st, method, keeptrials, output, compute_method, jackknife, log_dict)
 
 
@@ -344,10 +368,11 @@ def _run_stages(data, classes, st, method, keeptrials, output, compute_method, j
         # precision="auto": float64 transforms when the OUTPUT isolates a part of the complex coherency (its imaginary or real
         # part, its phase: 1.5e-7 of the modulus is not small against a part that nearly vanishes - as freqanalysis decides for
         # its own outputs), or when the DATA ask for them (CrossSpectra.needs_float64)
-        if (batched and hs.requested_precision() is None and method in ("coh", "granger") + phaseMethods
+        if (batched and hs.requested_precision() is None and method in ("coh", "granger") + phaseMethods + directedMethods
                 and isinstance(data, AnalogData)
                 and ((method == "coh" and output in ("imag", "angle", "real"))
-                     or (hasattr(st, "needs_float64") and st.needs_float64(data, method)))):
+                     or (hasattr(st, "needs_float64")
+                         and st.needs_float64(data, "granger" if method in directedMethods else method)))):
             stack.enter_context(hs.soft_reference())
         if method == "coh" and output in ("imag", "angle") and batched:
             from .. import backend
@@ -366,6 +391,10 @@ def _run_stages_impl(data, classes, st, method, keeptrials, output, compute_meth
         if "granger" not in classes:
             raise NotImplementedError("Wilson/Granger kernels are not part of this build")
         av = classes["granger"](rtol=5e-6, nIter=100, cond_max=1e4)
+    elif method in directedMethods:
+        if method not in classes:
+            raise NotImplementedError("Wilson/Granger kernels are not part of this build")
+        av = classes[method](output=output, rtol=5e-6, nIter=100, cond_max=1e4)
     else:
         av = None
 

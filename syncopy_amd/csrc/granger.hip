@@ -418,6 +418,38 @@ extern "C" int spyhip_granger(spyhip_ctx* ctx, const void* csd_d, int nfreq, int
 
 extern "C" int spyhip_granger_last_iterations(const spyhip_ctx* ctx) { return ctx ? ctx->granger_iters : -1; }
 
+// Batched inverse of `batch` n x n complex128 matrices with the kernels of the iteration: the block kernel of the size
+// class (inv_route) first, the partially pivoted kernel for the whole batch if any matrix flagged a tiny pivot - what
+// step_g's callers do.  The flags, and for dst == src a copy of the input (the repeat starts from it), live in the
+// context's arena.  A zero pivot of the pivoted kernel is a singular matrix: -7.
+extern "C" int spyhip_zinv(spyhip_ctx* ctx, const void* src_d, void* dst_d, int batch, int n) {
+    if (!ctx || !src_d || !dst_d) { spy::set_error("zinv: null argument"); return -1; }
+    if (batch < 1 || n < 1) { spy::set_error("zinv: bad shape"); return -1; }
+    SPY_HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)batch * n * n * sizeof(cd), flags = ((size_t)batch * sizeof(int) + 255) & ~(size_t)255;
+    const bool in_place = src_d == dst_d;
+    if (!reserve_arena(ctx, flags + (in_place ? bytes : 0))) { spy::set_error("zinv: out of device memory (%zu bytes)", flags + bytes); return -2; }
+    int* const inf = static_cast<int*>(ctx->arena);
+    const cd* src = as_cd(src_d);
+    if (in_place) {
+        cd* const keep = reinterpret_cast<cd*>(static_cast<char*>(ctx->arena) + flags);
+        SPY_HIP_CHECK(hipMemcpyAsync(keep, src_d, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        src = keep;
+    }
+    std::vector<int> h(batch);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if (invert(ctx, as_cd(dst_d), n, batch, inf, attempt == 0, src)) return -2;
+        SPY_HIP_CHECK(hipMemcpyAsync(h.data(), inf, batch * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        SPY_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        bool tiny_pivot = false;
+        for (int b = 0; b < batch; ++b) tiny_pivot = tiny_pivot || h[b] == 2;
+        if (!tiny_pivot) break;
+    }
+    for (int b = 0; b < batch; ++b)
+        if (h[b]) { spy::set_error("zinv: matrix %d of %d is singular", b, batch); return -7; }
+    return 0;
+}
+
 // =====================================================================================================================
 // The Wilson factorisation in steps, for frequency shards: every rank holds the bins [f_lo, f_lo + nf) of
 // the nftot rfft bins of the CSD.  Everything per frequency (regularisation, Cholesky factor, inverse, products, error)

@@ -10,7 +10,9 @@ spectralDTypes = {
 availableTapers = [w for w in windows.__all__ if w not in ("get_window", "exponential", "dpss")]
 availablePaddingOpt = ["maxperlen", "nextpow2"]
 availableMethods = ("mtmfft", "mtmconvol", "wavelet", "superlet", "welch")
-connectivityMethods = ("coh", "corr", "csd", "granger", "ppc", "plv", "pli", "wpli", "wpli_debiased")
+connectivityMethods = ("coh", "corr", "csd", "granger", "ppc", "plv", "pli", "wpli", "wpli_debiased", "dtf", "pdc")
 # ppc and its siblings beyond the reference: non-linear in the single-trial cross spectrum, accumulated over trials
 phaseMethods = ("ppc", "plv", "pli", "wpli", "wpli_debiased")
+# beyond the reference as well: directed measures of the Wilson factors, which take every rule of granger
+directedMethods = ("dtf", "pdc")
 connectivity_outputs = {"abs", "pow", "complex", "fourier", "angle", "real", "imag"}
