@@ -11,6 +11,8 @@ int csdh_run(hipStream_t stream, const float2* spec, long long nrows, int F, flo
              int nf, bool phase_exact) {
     if (nf <= 0 || nrows <= 0) return 0;
     if (nrows > 0x7fffffffLL) { spy::set_error("csd_accumulate: more than 2^31 - 1 rows in one call"); return -1; }
+    // (the kernel's loader fetches 16 bytes per lane; rs and fs below are even, so the base decides)
+    if (reinterpret_cast<uintptr_t>(spec) & 15u) { spy::set_error("csd_accumulate: 256-channel spectra must be 16-byte aligned"); return -1; }
     CsdhArgs a{};
     a.spec = spec; a.nrows = nrows; a.F = F; a.acc = acc; a.absmax = absmax; a.flags = flags; a.f0 = f0; a.nf = nf;
     a.rs = (long long)F * 256; a.fs = 256;

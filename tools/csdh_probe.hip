@@ -89,8 +89,8 @@ int main(int argc, char** argv) {
     if (getenv("CSDH_FMAJOR")) { a.rs = 256; a.fs = rows * 256; }
     if (getenv("CSDH_BLOCKED")) { a.rs = 256; a.fs = 32 * 256; /* rows of a 32-row block contiguous; blocks overlap: timing only */ }
     unsigned long long* stamps;
-    hipMalloc(&stamps, 4 * 8 * 8 * 8);
-    hipMemset(stamps, 0, 4 * 8 * 8 * 8);
+    hipMalloc(&stamps, (4 * 8 * 8 + 8) * 8);
+    hipMemset(stamps, 0, (4 * 8 * 8 + 8) * 8);
     a.stamps = stamps;
     hipFuncSetAttribute((const void*)spycsd::csdh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, spycsd::CSDH_LDS_BYTES);
     spycsd::csdh_kernel<<<F, 512, spycsd::CSDH_LDS_BYTES>>>(a);
@@ -99,18 +99,32 @@ int main(int argc, char** argv) {
 
 #ifdef CSDH_STAMPS
     {
-        std::vector<unsigned long long> h(4 * 8 * 8);
+        std::vector<unsigned long long> h(4 * 8 * 8 + 8);
         hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost);
         const unsigned long long t0 = h[0];
-        printf("timeline of block 0 (cycles since wave 0 entered chunk 20): points 0 chunk start, 1 after first tile, 2 before / 3 after the wait for loads A, 4 after conversion A + issue of loads B, 5 before / 6 after the wait for loads B, 7 before the barrier\n");
+        printf("timeline of block 0 (cycles since wave 0 entered chunk 20): points 0 chunk start, 1 after first tile, 7 before the barrier; loader waves also 2 before / 3 after the sub-tile that carries the conversion of phase 0, 4 after its LDS writes + the request of phase 2, 5 before the sub-tile that carries phase 3, 6 after its LDS writes + the request of the next chunk's phase 1 (heavy waves: -)\n");
         for (int c = 0; c < 4; ++c)
             for (int g = 0; g < 8; ++g) {
                 printf("chunk %d wave %d:", 20 + c, g);
-                for (int k = 0; k < 8; ++k) printf(" %7lld", (long long)(h[(c * 8 + g) * 8 + k] - t0));
+                for (int k = 0; k < 8; ++k) {
+                    if (h[(c * 8 + g) * 8 + k]) printf(" %7lld", (long long)(h[(c * 8 + g) * 8 + k] - t0));
+                    else printf(" %7s", "-");                       // a point this wave does not pass (a heavy wave's 2 ... 6)
+                }
                 printf("\n");
             }
+        // which waves share a SIMD (HW_ID: wave slot bits 3:0, SIMD 5:4, CU 11:8), and which of the two holds the lower slot
+        for (int g = 0; g < 8; ++g)
+            printf("wave %d: hw_id 0x%08llx  simd %llu  wave slot %llu  cu %llu\n", g, h[256 + g], (h[256 + g] >> 4) & 3, h[256 + g] & 15,
+                   (h[256 + g] >> 8) & 15);
     }
 #endif
+    {   // a fingerprint of the whole accumulator after the first launch: equal across builds = bit-identical results
+        std::vector<unsigned long long> hall((size_t)F * 65536);
+        hipMemcpy(hall.data(), acc, hall.size() * 8, hipMemcpyDeviceToHost);
+        unsigned long long fp = 1469598103934665603ull;
+        for (unsigned long long v : hall) fp = (fp ^ v) * 1099511628211ull;
+        printf("accumulator fingerprint after the first launch: %016llx\n", fp);
+    }
     // the same through the pre-split hand-over (csdhp_kernel.h): planes from csdhp_split_kernel, LDS-DMA, transpose reads
     float2* accp;
     uint4* planes;

@@ -39,7 +39,7 @@ template <int G>
 __device__ __forceinline__ void csdhp_wave(const CsdhArgs& a, char* lds, int f, int lane) {
     using TAB = HTab;
     using PL = HPlan<G>;
-    constexpr int NT = TAB::NT, ND = TAB::ND;
+    constexpr int NT = TAB::nt(G), ND = csdh_npd(G);
     int* const vword = reinterpret_cast<int*>(lds + 2 * CSDHP_BUF);
     if (G == 0 && lane == 0) *vword = 1;
 
