@@ -152,6 +152,17 @@ extern "C" int spyhip_cwt_plan_destroy(spyhip_cwt_plan* p) {
     return 0;
 }
 
+// what a call of `nseg` segments asks of the route: the plan's options, the chip and the launch limits of its context
+static spycwt::ExecQuery exec_query(const spyhip_cwt_plan* p, int nseg, int accumulate) {
+    spycwt::ExecQuery q;
+    q.nseg = nseg; q.accumulate = accumulate; q.direct = p->direct; q.precision64 = p->precision64; q.L64 = p->L64;
+    q.num_cu = p->ctx->num_cu;
+    const spyhip_limits& lim = p->ctx->limits;
+    if (lim.cwt_stage_bytes > 0) q.stage_budget = (size_t)lim.cwt_stage_bytes;
+    if (lim.cwt_work64_bytes > 0) q.work_budget = (size_t)lim.cwt_work64_bytes;
+    return q;
+}
+
 extern "C" int spyhip_cwt_exec(spyhip_cwt_plan* p, const float* data_d, int64_t ld, const int32_t* chan_idx_d,
                                const int64_t* seg_start_d, const int64_t* trial_lo_d, const int64_t* trial_hi_d,
                                int nseg, void* out_d, int accumulate) {
@@ -161,10 +172,7 @@ extern "C" int spyhip_cwt_exec(spyhip_cwt_plan* p, const float* data_d, int64_t 
     SPY_HIP_CHECK(hipSetDevice(p->ctx->device));
     const hipStream_t st = p->ctx->stream;
     const Plan& pl = p->r;
-    ExecQuery q;
-    q.nseg = nseg; q.accumulate = accumulate; q.direct = p->direct; q.precision64 = p->precision64; q.L64 = p->L64;
-    q.num_cu = p->ctx->num_cu;
-    const ExecRoute r = exec_route(pl, q);
+    const ExecRoute r = exec_route(pl, exec_query(p, nseg, accumulate));
     if (r.sum_set && p->groups_sum.empty() && upload_groups(p, pl.groups_sum, p->groups_sum)) {
         p->groups_sum.clear();
         return -2;

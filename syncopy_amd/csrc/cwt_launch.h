@@ -1,5 +1,5 @@
-// The kernel instance behind a step of the wavelet route (cwt_route.h), declared once from the engine list for the
-// library (cwt.hip) and the kernel emulator: f(kernel, threads per workgroup, dynamic LDS bytes).  -1: no such instance.
+// The kernel instance behind a step of the wavelet route (cwt_route.h), declared once from the engine list for
+// cwt.hip: f(kernel, threads per workgroup, dynamic LDS bytes).  -1: no such instance.
 #pragma once
 #include "cwt_kernel.h"
 #include "cwt64_kernel.h"

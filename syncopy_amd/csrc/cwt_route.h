@@ -1,8 +1,8 @@
 // Host decisions of the wavelet transform (K3): the sampled taps of a scale, which block engine a scale runs on, which
 // scales share a launch, how long kernels are cut, which staging row a scale gets, and the ordered steps of a call with
 // their grids and buffer sizes.  Pure logic on integers and host vectors, no HIP header and no runtime call, so that the
-// policy is testable on any host (tests/test_cwt_route.py) and shared by the library (cwt.hip walks the steps with
-// hipLaunchKernelGGL) and the kernel emulator (tests/emu/emu_kernels.cpp walks the same steps with emu::launch).
+// policy is testable on any host (tests/test_cwt_route.py).  cwt.hip walks the steps with hipLaunchKernelGGL, on the
+// device and, in the kernel emulator (tests/emu/cwt_emu.cpp), on the CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>

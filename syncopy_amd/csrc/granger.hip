@@ -264,7 +264,8 @@ int fused_check(Wilson& w, int nbins, long long stride) {
 // the full check runs as soon as the subset passes - same decisions, ~1/8 of the 3.1 ms per iteration at 256 channels x
 // 2049 frequencies.  Ends with the iteration's synchronize.
 int step_error(Wilson& w, const spywil::ErrRoute& er, double rtol, double* err, bool* subset_only) {
-    std::vector<double> hp(er.fused ? 1 : spywil::NRED);
+    const size_t nred = (size_t)std::min<int64_t>(spywil::NRED, w.ctx->limits.elementwise_blocks);     // (relerr_kernel strides)
+    std::vector<double> hp(er.fused ? 1 : nred);
     *subset_only = false;
     if (er.subset_first) {
         if (fused_check(w, er.subset_bins, 8)) return -2;
@@ -276,7 +277,7 @@ int step_error(Wilson& w, const spywil::ErrRoute& er, double rtol, double* err, 
         if (!*subset_only && fused_check(w, w.F, 1)) return -2;
     } else {
         if (gemm(w.ctx, w.psi, w.psi, w.T1, w.n, w.F, w.nn(), w.nn(), w.nn(), 1, 0)) return -2;          // psi psi^H
-        if (launch(w.ctx, spywil::relerr_kernel, dim3(spywil::NRED), 256, 0, w.A, w.T1, (long long)w.tot(), w.part)) return -2;
+        if (launch(w.ctx, spywil::relerr_kernel, dim3((unsigned)nred), 256, 0, w.A, w.T1, (long long)w.tot(), w.part)) return -2;
     }
     SPY_HIP_CHECK(hipMemcpyAsync(hp.data(), w.part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, w.ctx->stream));
     SPY_HIP_CHECK(hipStreamSynchronize(w.ctx->stream));

@@ -1,6 +1,6 @@
 // Which kernels serve the Wilson / Granger stage (K6), with which grid and how much LDS, and where the work arrays of
-// spyhip_granger lie: pure integer logic, no HIP header and no runtime call, so that the launcher (granger.hip), the kernel
-// emulator (tests/emu/emu_kernels.cpp) and the route test (tests/emu/granger_route_shim.cpp) read one decision.
+// spyhip_granger lie: pure integer logic, no HIP header and no runtime call, so that the launcher (granger.hip, which
+// the kernel emulator runs: tests/emu/granger_emu.cpp) and the route test (tests/emu/granger_route_shim.cpp) read one decision.
 // The constexpr functions are callable from device code as they stand (granger_kernels.h, wilson_plus_kernel.h).
 // tests/test_granger_route.py holds the resulting table of size classes for the 160 KiB of LDS of the MI355X.
 #pragma once

@@ -18,11 +18,14 @@
 // (the CPU emulator of tests/emu lowers them so that the chunk loops and grid-stride loops run at test sizes).
 struct spyhip_limits {
     int64_t grid_yz = 65535;            // blocks along grid.y / grid.z
-    int64_t elementwise_blocks = 4096;  // workgroups of the grid-stride kernels of stats.hip and of the partial-sum reduction
-                                        // of csd.hip; its tril and coherence launches take 4 x and 2 x as many
+    int64_t elementwise_blocks = 4096;  // workgroups of the grid-stride kernels of stats.hip, of the partial-sum reduction
+                                        // of csd.hip (its tril and coherence launches take 4 x and 2 x as many) and of
+                                        // the error reduction of granger.hip (spywil::NRED at the most)
     int64_t workgroups = 65535;         // workgroups of the median, variance and transposition launches and of the rank-1
                                         // cross-spectral update
     int64_t any64_chunk = INT64_MAX;    // work arrays of one float64 Hilbert launch, on top of spyhil::any64_chunk
+    int64_t cwt_stage_bytes = 0;        // staging of one chunk of segments of spyhip_cwt_exec; 0: spycwt::STAGE_BUDGET
+    int64_t cwt_work64_bytes = 0;       // work arrays of one cwt64_kernel launch; 0: spycwt::WORK64_BUDGET
 };
 
 struct spyhip_ctx {

@@ -13,6 +13,25 @@ from oracle import spy_oracle as O
 CWT64_ULPS = {"fourier": 1, "real": 1, "imag": 1, "pow": 4, "abs": 4}
 
 
+def cwt64_taps(nsig, scales, dt, w0=6.0, family=None, order=None, sl_cycles=None):
+    """The sampled kernels of spyhip_cwt_plan_create trimmed to the taps that can overlap a signal of nsig samples, and
+    each trimmed kernel's "same" offset: [(taps, centre)].  family None / "Paul" / "DOG" as O.cwt_kernel; `sl_cycles`:
+    MorletSL (O.cwt_sl)."""
+    out = []
+    for s in scales:
+        if sl_cycles is None:
+            h = O.cwt_kernel(s, dt, w0, family, order)
+        else:
+            M = 10 * s * sl_cycles / dt
+            t = np.arange((-M + 1) / 2.0, (M + 1) / 2.0) * dt
+            h = dt ** 0.5 / (4 * np.pi) * O.morlet_sl(t, s, sl_cycles)
+        h = np.asarray(h, dtype=np.complex128)
+        c = (h.size - 1) // 2
+        m0, m1 = max(0, c - (nsig - 1)), min(h.size, c + nsig)
+        out.append((h[m0:m1], c - m0))
+    return out
+
+
 def cwt64_ref(data, ss, lo, hi, nsig, scales, detrend, output, chan_idx=None, family=None, order=None, sl_cycles=None,
               convert=True):
     """Per segment: O.cwt of the float32-detrended trial in float64 (complex64 storage) -> (nseg, nsig, nscales, nchan)."""

@@ -230,6 +230,14 @@ int cwt_taps(int family, double p0, double p1, double scale, double dt, int nsig
 
 int cwt_block_length(int ntaps, int floor) { return block_length(ntaps, floor); }
 
+// L of spyhip_cwt_plan_set_precision for these tap counts
+long long cwt_conv_length64(int nsig, const int* ntaps, int nscales) { return conv_length64(nsig, std::vector<int>(ntaps, ntaps + nscales)); }
+
+// the plan-creation rule for the direct kernels
+int cwt_direct_fits(const int* tpos, int nsig, const int* V, int ngroups, unsigned long long rowb, unsigned long long chanb) {
+    return spycwt::cwt_direct_fits(tpos, nsig, V, ngroups, rowb, chanb) ? 1 : 0;
+}
+
 // plan: one line per group (cwt_route_text.h); message: the plan's error text, or the shim's verdict on its invariants
 int cwt_plan_text(int family, double p0, double p1, const double* scales, int nscales, double dt, int nsig, int nchan, int output,
                   int detrend, const int* tpos, char* plan, char* message, int cap) {

@@ -20,10 +20,6 @@ thread_local BlockCtx* t_ctx = nullptr;
 #include "../../syncopy_amd/csrc/mtmfft_mixed.h"
 #include "../../syncopy_amd/csrc/mtmfft_long.h"
 #include "../../syncopy_amd/csrc/mtmfft_declong.h"
-#include "../../syncopy_amd/csrc/cwt_launch.h"
-#include "cwt_route_text.h"
-#include "../../syncopy_amd/csrc/granger_kernels.h"
-#include "../../syncopy_amd/csrc/wilson_plus_kernel.h"
 #include "../../syncopy_amd/csrc/mtmfft_dec64_cfg.h"
 #include "../../syncopy_amd/csrc/mtmfft_dec_cfg.h"
 #include "../../syncopy_amd/csrc/mtmfft_tables.h"
@@ -35,264 +31,6 @@ void set_error(const char*, ...) {}
 
 using spyfft::GenPlan;
 using spyfft::MtmArgs;
-
-// plus4_kernel<LOG2L> with the grid, threads and LDS of its route (granger_route.h)
-template <int LOG2L>
-void run_plus4(const spywil::PlusRoute& r, const double* g, int F, long long nent, const double* tw, double* gp, double* g0) {
-    emu::launch(dim3((unsigned)r.grid), dim3(r.threads), r.lds, [&] {
-        spywil::plus4_kernel<LOG2L>(reinterpret_cast<const spywil::cd*>(g), F, nent, reinterpret_cast<const spywil::cd*>(tw),
-                                    reinterpret_cast<spywil::cd*>(gp), reinterpret_cast<spywil::cd*>(g0)); });
-}
-
-extern "C" {
-// spyhip_cwt_plan_create* + set_direct / set_precision + spyhip_cwt_exec for the emulated kernels: the taps, the plan and the
-// steps of cwt_route.h (the ones cwt.hip uploads and launches), walked with emu::launch on host buffers.  family, p0, p1:
-// spycwt::sample_taps; num_cu and the two byte budgets as spycwt::ExecQuery (<= 0: the library's).  `trace`: one line per
-// step (cwt_route_text.h).  Returns the route's error code.
-int emu_cwt(const float* data, long long ld, const int* chan_idx, const long long* seg_start, const long long* trial_lo,
-            const long long* trial_hi, int nseg, int nsig, int nchan, int nscales, const double* scales, double dt, int family,
-            double p0, double p1, int detrend, int out_kind, const int* tpos, int ntime_out, void* out, int accumulate,
-            int direct, int precision64, long long num_cu, long long stage_budget, long long work_budget, char* trace, int cap) {
-    using namespace spycwt;
-    std::vector<Taps> taps;
-    std::vector<int> ntaps, centre;
-    for (int s = 0; s < nscales; ++s) {
-        taps.push_back(sample_taps(family, p0, p1, scales[s], dt, nsig));
-        ntaps.push_back((int)taps[s].re.size());
-        centre.push_back(taps[s].c);
-    }
-    const Plan pl = plan_route(nsig, nchan, out_kind, detrend, ntaps, centre, tpos);
-    if (pl.err) return pl.err;
-    ExecQuery q;
-    q.nseg = nseg; q.accumulate = accumulate; q.direct = direct && pl.direct_ok; q.precision64 = precision64 != 0;
-    if (num_cu > 0) q.num_cu = num_cu;
-    if (stage_budget > 0) q.stage_budget = (size_t)stage_budget;
-    if (work_budget > 0) q.work_budget = (size_t)work_budget;
-    spyfft::Cwt64Args fa{};
-    std::vector<double2> tw64, hspec64;
-    if (q.precision64) {                     // spyhip_cwt_plan_set_precision
-        q.L64 = conv_length64(nsig, ntaps);
-        if (q.L64 > MAX_L64 || !spywil::plus_plan((int)q.L64, &fa.plan)) return -3;
-        tw64 = spy::twiddle_table<double2>((int)q.L64);
-        hspec64.resize((size_t)nscales * q.L64);
-        for (int s = 0; s < nscales; ++s) kernel_spectrum(taps[s], 0, taps[s].re.size(), (size_t)q.L64, &hspec64[(size_t)s * q.L64]);
-        fa.L = (int)q.L64; fa.tw64 = tw64.data(); fa.hspec64 = hspec64.data(); fa.centre = pl.centre.data();
-    }
-    const ExecRoute r = exec_route(pl, q);
-    if (trace) {
-        std::string t;
-        for (const Step& s : r.steps) t += render_step(pl, r, s) + "\n";
-        std::snprintf(trace, cap, "%s", t.c_str());
-    }
-    // the tables upload_groups of cwt.hip builds for the group set in use
-    const std::vector<Group>& groups = r.sum_set ? pl.groups_sum : pl.groups;
-    struct Tables { std::vector<float2> tw, hspec; };
-    std::vector<Tables> tables(q.precision64 ? 0 : groups.size());
-    for (size_t gi = 0; gi < tables.size(); ++gi) {
-        const Group& g = groups[gi];
-        const size_t NB = (size_t)1 << g.log2n;
-        tables[gi].tw = spy::twiddle_table<float2>((int)NB);
-        tables[gi].hspec.resize(g.nscales() * NB);
-        for (int k = 0; k < g.nscales(); ++k) {
-            const Taps& t = taps[g.scale_ids[k]];
-            const bool piece = g.long_idx >= 0;
-            kernel_spectrum(t, piece ? g.tap0 : 0, piece ? g.ntaps : t.re.size(), NB, &tables[gi].hspec[k * NB]);
-        }
-    }
-    std::vector<double> trend(r.trend), trend_part(r.trend * TREND_SPLITS);
-    std::vector<char> stage(r.stage_bytes);
-    std::vector<float2> stage_long(r.stage_long);
-    std::vector<float> xt(r.xt);
-    std::vector<double2> work(r.work64);
-    std::vector<int> fl;
-    spyfft::CwtArgs a{};
-    a.data = data; a.ld = ld; a.chan_idx = chan_idx;
-    a.nsig = nsig; a.nchan = nchan; a.nscales = nscales; a.nscales_total = nscales;
-    a.detrend = detrend; a.out_kind = out_kind; a.tpos = tpos;
-    if (tpos) { fl = tfloor(tpos, nsig); a.tfloor = fl.data(); }
-    a.ntime_out = tpos ? ntime_out : nsig; a.out = out; a.accumulate = accumulate;
-    a.stage = stage.data();
-    fa.work = work.data();
-    for (const Step& s : r.steps) {
-        spyfft::CwtArgs c = a;
-        c.seg0 = s.seg0; c.nseg = s.nseg;
-        c.seg_start = seg_start + s.seg0; c.trial_lo = trial_lo + s.seg0; c.trial_hi = trial_hi + s.seg0;
-        if (detrend >= 0) c.trend = trend.data() + (size_t)s.seg0 * nchan * 2;
-        if (r.xt && s.kind == StepKind::TRANSFORM) c.xt = xt.data();
-        const dim3 grid((unsigned)s.gx, (unsigned)s.gy, (unsigned)s.gz);
-        switch (s.kind) {
-            case StepKind::MEAN_NP: emu::launch(grid, dim3(64), 0, [&] { spyfft::cwt_mean_np_kernel(c, trend.data()); }); break;
-            case StepKind::TREND:
-                emu::launch(grid, dim3(256), 0, [&] { spyfft::cwt_trend_partial_kernel(c, trend_part.data()); });
-                emu::launch(dim3((unsigned)(((size_t)nseg * nchan + 255) / 256)), dim3(256), 0,
-                            [&] { spyfft::cwt_trend_final_kernel(c, trend_part.data(), trend.data()); });
-                break;
-            case StepKind::INPUT_COPY: emu::launch(grid, dim3(256), 0, [&] { spyfft::cwt_stage_input_kernel(c, xt.data()); }); break;
-            case StepKind::CWT64:
-                fa.c = c; fa.wg0 = s.wg0;
-                with_cwt64_kernel(s.outk, [&](auto kern) { emu::launch(grid, dim3(256), 0, [&] { kern(fa); }); return 0; });
-                break;
-            case StepKind::TRANSFORM: {
-                const Group& gr = groups[s.group];
-                c.nscales = gr.nscales();
-                c.sidx = s.sidx == Sidx::COMPACT ? gr.sidx_stage.data() : gr.sidx.data();
-                c.nscales_total = s.nrows;
-                c.tw = tables[s.group].tw.data(); c.hspec = tables[s.group].hspec.data(); c.cshift = gr.cshift.data();
-                c.V = gr.V; c.halo = gr.halo; c.nblocks = gr.nblocks;
-                c.stage_add = s.add;
-                if (s.target == Target::LONG_SIDE) c.stage = stage_long.data();
-                const int rc = with_transform_kernel(gr.log2n, s.engine, s.outk, [&](auto kern, int threads, size_t lds) {
-                    emu::launch(grid, dim3(threads), lds, [&] { kern(c); });
-                    return 0;
-                });
-                if (rc) return rc;
-                break;
-            }
-            case StepKind::LONG_CONVERT:
-                emu::launch(grid, dim3(256), 0, [&] {
-                    spyfft::cwt_long_convert_kernel(stage_long.data(), s.sidx == Sidx::COMPACT ? pl.lrow.data() : pl.long_scales.data(),
-                                                    (int)pl.long_scales.size(), s.nseg, s.nrows, nchan, nsig, out_kind,
-                                                    reinterpret_cast<float*>(stage.data()));
-                });
-                break;
-            case StepKind::SCATTER:
-                c.nseg = s.nsets; c.nscales = s.nrows;
-                if (s.compact) { c.smap = pl.staged.data(); c.nscales_out = nscales; }
-                with_scatter_kernel(s.scatter, [&](auto kern) { emu::launch(grid, dim3(256), 0, [&] { kern(c); }); return 0; });
-                break;
-        }
-    }
-    return r.err;
-}
-
-// L of spyhip_cwt_plan_set_precision for these tap counts
-long long emu_cwt_conv_length64(int nsig, const int* ntaps, int nscales) {
-    return spycwt::conv_length64(nsig, std::vector<int>(ntaps, ntaps + nscales));
-}
-
-// the plan-creation rule for the direct kernels (cwt_route.h)
-int emu_cwt_direct_fits(const int* tpos, int nsig, const int* V, int ngroups, unsigned long long rowb, unsigned long long chanb) {
-    return spycwt::cwt_direct_fits(tpos, nsig, V, ngroups, rowb, chanb) ? 1 : 0;
-}
-
-// ---- Wilson / Granger kernels.  Which kernel an entry runs, with which grid and LDS, is the decision of granger_route.h
-// that granger.hip launches by; `name` (64 bytes, or NULL) receives the kernel's name.
-using spywil::cd;
-static void w_name(char* name, const char* s) { if (name) std::snprintf(name, 64, "%s", s); }
-void emu_w_widen(const float* in, double* out, int C, long long n, double eps) {
-    emu::launch(dim3(4), dim3(256), 0, [&] { spywil::widen_kernel(reinterpret_cast<const float2*>(in), reinterpret_cast<cd*>(out), C, n, eps); });
-}
-// Badd (n x n) joins op(B); with Ref the return value is max |Ref - A op(B)| / |Ref| and no product is stored (both: n >= 48)
-double emu_w_gemm(const double* A_, const double* B_, double* C_, int n, int batch, long long sA, long long sB, long long sC, int opB,
-                  int addI, const double* Badd_, const double* Ref_, char* name) {
-    const cd *A = reinterpret_cast<const cd*>(A_), *B = reinterpret_cast<const cd*>(B_), *Badd = reinterpret_cast<const cd*>(Badd_),
-             *Ref = reinterpret_cast<const cd*>(Ref_);
-    cd* Cm = reinterpret_cast<cd*>(C_);
-    const spywil::GemmRoute r = spywil::gemm_route(n, batch, opB, A == B && sA == sB, Badd != nullptr, Ref != nullptr);
-    w_name(name, r.name);
-    std::vector<double> partv((size_t)r.ntiles * batch + 1, -1.0);
-    double* part = Ref ? partv.data() : nullptr;
-    const dim3 grid(r.grid.x, r.grid.y, r.grid.z);
-    switch (r.kernel) {
-        case spywil::Gemm::TILED: emu::launch(grid, dim3(r.threads), r.lds, [&] { spywil::zgemm_kernel(A, B, Cm, n, sA, sB, sC, opB, addI); }); break;
-        case spywil::Gemm::MFMA0: emu::launch(grid, dim3(r.threads), r.lds, [&] { spywil::zgemm_mfma_kernel<0>(A, B, Cm, n, sA, sB, sC, opB, addI, Badd, Ref, part, batch); }); break;
-        case spywil::Gemm::MFMA1: emu::launch(grid, dim3(r.threads), r.lds, [&] { spywil::zgemm_mfma_kernel<1>(A, B, Cm, n, sA, sB, sC, opB, addI, Badd, Ref, part, batch); }); break;
-        case spywil::Gemm::MFMA2: emu::launch(grid, dim3(r.threads), r.lds, [&] { spywil::zgemm_mfma_kernel<2>(A, B, Cm, n, sA, sB, sC, opB, addI, Badd, Ref, part, batch); }); break;
-        case spywil::Gemm::MFMA3: emu::launch(grid, dim3(r.threads), r.lds, [&] { spywil::zgemm_mfma_kernel<3>(A, B, Cm, n, sA, sB, sC, opB, addI, Badd, Ref, part, batch); }); break;
-    }
-    if (r.kernel != spywil::Gemm::MFMA2) return 0.0;
-    double out = -1.0;
-    emu::launch(dim3(1), dim3(256), 0, [&] { spywil::maxred_kernel(part, r.ntiles * batch, &out); });
-    return out;
-}
-void emu_w_skew(const double* g0, double* S, double* g0S, int n) {
-    emu::launch(dim3((n * n + 255) / 256), dim3(256), 0, [&] { spywil::skew_kernel(reinterpret_cast<const cd*>(g0), reinterpret_cast<cd*>(S), reinterpret_cast<cd*>(g0S), n); });
-}
-// inverse of `batch` matrices in M, out of place from a copy of the input as the Wilson iteration calls it (M is
-// overwritten first, so a kernel that read M instead of its source would show)
-void emu_w_inv(double* M_, int n, int batch, int* info, int blocked, unsigned long long lds_per_block, char* name) {
-    const spywil::InvRoute r = spywil::inv_route(n, blocked != 0, true, (size_t)lds_per_block);
-    w_name(name, r.name);
-    const size_t cnt = (size_t)batch * n * n;
-    cd* M = reinterpret_cast<cd*>(M_);
-    std::vector<cd> srcv(M, M + cnt);
-    const cd* src = srcv.data();
-    std::fill(M_, M_ + 2 * cnt, -777.0);
-    if (r.copy_src) std::copy(src, src + cnt, M);
-    switch (r.kernel) {
-        case spywil::Inv::MFMA64: emu::launch(dim3(batch), dim3(r.threads), r.lds, [&] { spywil::zinv64_mfma_kernel(M, src, n, info); }); break;
-        case spywil::Inv::MFMA32: emu::launch(dim3(batch), dim3(r.threads), r.lds, [&] { spywil::zinv_mfma_kernel(M, src, n, info); }); break;
-        case spywil::Inv::BLOCKED16: emu::launch(dim3(batch), dim3(r.threads), r.lds, [&] { spywil::zinv_blocked_kernel(M, n, info); }); break;
-        case spywil::Inv::PIVOTED: emu::launch(dim3(batch), dim3(r.threads), r.lds, [&] { spywil::zinv_kernel(M, n, info); }); break;
-    }
-}
-void emu_w_chol(double* M, int n, int batch, int* info, unsigned long long lds_per_block, char* name) {
-    const spywil::CholRoute r = spywil::chol_route(n, (size_t)lds_per_block);
-    w_name(name, r.name);
-    if (r.kernel == spywil::Chol::PANEL) emu::launch(dim3(batch), dim3(r.threads), r.lds, [&] { spywil::zchol_panel_kernel(reinterpret_cast<cd*>(M), n, info); });
-    else emu::launch(dim3(batch), dim3(r.threads), r.lds, [&] { spywil::zchol_kernel(reinterpret_cast<cd*>(M), n, info); });
-}
-void emu_w_gamma0(const double* A, int F, int n, double* out) {
-    emu::launch(dim3((n * n + 255) / 256), dim3(256), 0, [&] { spywil::gamma0_kernel(reinterpret_cast<const cd*>(A), F, n, reinterpret_cast<cd*>(out), 0, F); });
-}
-// the plus operator on the kernel family of the route; generic != 0: plus_kernel whatever the length (the radix-4 kernel
-// plus4_kernel is compared with).  Returns -3 where no radix schedule exists.
-int emu_w_plus(const double* g_, int F, int n, const double* tw_, double* gp_, double* g0_, unsigned long long lds_per_block, int num_cu,
-               int generic, char* name) {
-    const cd *g = reinterpret_cast<const cd*>(g_), *tw = reinterpret_cast<const cd*>(tw_);
-    cd *gp = reinterpret_cast<cd*>(gp_), *g0 = reinterpret_cast<cd*>(g0_);
-    const int L = 2 * (F - 1);
-    const long long nent = (long long)n * n;
-    spywil::PlusPlan pl{};
-    if (!spywil::plus_plan(L, &pl)) return -3;
-    spywil::PlusRoute r = spywil::plus_route(L, nent, (size_t)lds_per_block, num_cu);
-    if (generic) { r = spywil::PlusRoute(); r.name = "spywil::plus_kernel"; r.grid = nent; r.lds = (size_t)2 * L * 16; }
-    w_name(name, r.name);
-    switch (r.kernel) {
-        case spywil::Plus::PLUS4:
-            switch (r.log2l) {
-                case 8: run_plus4<8>(r, g_, F, nent, tw_, gp_, g0_); break;
-                case 9: run_plus4<9>(r, g_, F, nent, tw_, gp_, g0_); break;
-                case 10: run_plus4<10>(r, g_, F, nent, tw_, gp_, g0_); break;
-                case 11: run_plus4<11>(r, g_, F, nent, tw_, gp_, g0_); break;
-                default: run_plus4<12>(r, g_, F, nent, tw_, gp_, g0_); break;
-            }
-            break;
-        case spywil::Plus::LDS:
-            emu::launch(dim3((unsigned)r.grid), dim3(r.threads), r.lds, [&] { spywil::plus_kernel(g, F, nent, pl, tw, gp, g0); });
-            break;
-        case spywil::Plus::LONG: {
-            std::vector<cd> scr(r.scratch_bytes / sizeof(cd));
-            for (long long e0 = 0; e0 < nent; e0 += r.chunk)
-                emu::launch(dim3((unsigned)std::min(r.chunk, nent - e0)), dim3(r.threads), 0,
-                            [&] { spywil::plus_long_kernel(g, F, nent, pl, tw, gp, g0, scr.data(), e0); });
-            break;
-        }
-    }
-    return 0;
-}
-// the convergence check of the Wilson iteration for n channels and F bins: out = {fused, subset first, subset bins}
-void emu_w_err_route(int n, int F, int full_check_forced, int* out) {
-    const spywil::ErrRoute r = spywil::err_route(n, F, full_check_forced != 0);
-    out[0] = r.fused; out[1] = r.subset_first; out[2] = r.subset_bins;
-}
-void emu_w_addS(double* gp, const double* g0, double* out0, int F, int n) {
-    emu::launch(dim3(4), dim3(256), 0, [&] { spywil::add_S_kernel(reinterpret_cast<cd*>(gp), reinterpret_cast<const cd*>(g0), reinterpret_cast<cd*>(out0), F, n); });
-}
-double emu_w_relerr(const double* A, const double* B, long long n) {
-    std::vector<double> part(8);
-    emu::launch(dim3(8), dim3(256), 0, [&] { spywil::relerr_kernel(reinterpret_cast<const cd*>(A), reinterpret_cast<const cd*>(B), n, part.data()); });
-    double m = 0; for (double v : part) if (v > m || v != v) m = v;
-    return m;
-}
-void emu_w_power(const double* M, int n, int batch, int iters, double* lam) {
-    emu::launch(dim3(batch), dim3(256), (size_t)2 * n * 16, [&] { spywil::power_kernel(reinterpret_cast<const cd*>(M), n, iters, lam); });
-}
-void emu_w_granger(const double* CSD, const double* H, const double* Sigma, int F, int n, float* out) {
-    emu::launch(dim3(4), dim3(256), 0, [&] { spywil::granger_kernel(reinterpret_cast<const cd*>(CSD), reinterpret_cast<const cd*>(H), reinterpret_cast<const cd*>(Sigma), F, n, out); });
-}
-
-}  // extern "C"
 
 // ---- The tapered FFT (K1): one emulated spyhip_fft_plan_create + plan options + spyhip_fft_exec.  The route
 // (mtmfft_route.h), the tables (mtmfft_tables.h), the grids and the mode dispatch (spy_launch.h) and the schedule names

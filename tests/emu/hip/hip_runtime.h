@@ -1,15 +1,19 @@
 // Stand-in for <hip/hip_runtime.h>, TEST INFRASTRUCTURE ONLY (see ../hip_emu.h).  With tests/emu first on the include
 // path the library's own .hip files compile as C++: their launchers run on the CPU and their kernels under emu::launch.
 // It names what the host code of the preprocessing, statistics, covariance, resampling, histogram, Hilbert, cross-spectral,
-// phase-consistency and lag launchers (and csrc/spy_common.h under them) uses of the runtime, nothing else; "device"
+// phase-consistency, lag, wavelet and Wilson / Granger launchers (and csrc/spy_common.h under them) uses of the runtime, nothing else; "device"
 // memory is host memory and the one stream is synchronous.  Define one translation unit per emulator library: the launch log below lives in it.
 #pragma once
 #include "../hip_emu.h"
+#include <algorithm>
+
+using std::max;      // (device code calls the runtime's unqualified min / max)
+using std::min;
 
 typedef struct emuStream* hipStream_t;
 typedef struct emuEvent* hipEvent_t;
 enum hipError_t { hipSuccess = 0, hipErrorOutOfMemory = 2 };
-enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2 };
+enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3 };
 enum { hipEventDisableTiming = 2 };
 enum hipFuncAttribute { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
 inline hipError_t hipSetDevice(int) { return hipSuccess; }

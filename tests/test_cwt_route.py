@@ -1,7 +1,7 @@
 """The host decisions of the wavelet transform - taps, block engines, groups, pieces, staging rows and the ordered steps
 of a call: the pure route of syncopy_amd/csrc/cwt_route.h, compiled with the host compiler alone (no HIP, no device) and
-asked through a small C shim (tests/emu/cwt_route_shim.cpp).  The library and the kernel emulator both walk the steps this
-header returns."""
+asked through a small C shim (tests/emu/cwt_route_shim.cpp).  The library walks the steps this header returns, and the
+kernel emulator runs the library (tests/emu/cwt_emu.cpp)."""
 import ctypes as C
 import os
 import sys
@@ -269,7 +269,7 @@ def test_every_plan_and_call_keeps_the_invariants(lib):
 
 
 # ---- the C++ tap sampling against the oracle's kernels -----------------------------------------------------------------
-# (family, p0, p1) of spycwt::sample_taps and the arguments of emu_driver.cwt64_taps
+# (family, p0, p1) of spycwt::sample_taps and the arguments of cwt64_ref.cwt64_taps
 FAMILIES = [("Morlet", (0, 6.0, 0.0), dict(w0=6.0)), ("MorletSL", (1, 3.0, 5.0), dict(sl_cycles=3.0)),
             ("Paul4", (2, 4.0, 0.0), dict(family="Paul", order=4)), ("DOG2", (3, 2.0, 0.0), dict(family="DOG", order=2)),
             ("DOG6", (3, 6.0, 0.0), dict(family="DOG", order=6))]
@@ -292,10 +292,10 @@ def test_tap_sampling_agrees_with_the_oracle(lib, name, fam, kw):
     2^-51.2 (DOG 2), 2^-50.7 (DOG 6) of the largest tap at these scales.  A third way of rounding the same argument (the
     C++ forms x = (t0 + m) dt / s, and atan / pow for Paul) is held to 4x the largest of these: 2^-47 of the largest tap,
     absolutely, per tap."""
-    import emu_driver as E
+    from cwt64_ref import cwt64_taps
     scales = np.array([0.004, 0.03, 0.11]) / (3.0 if name == "MorletSL" else 1.0)
     for nsig in (90, 5000):
-        ref = E.cwt64_taps(nsig, scales, 1e-3, **kw)
+        ref = cwt64_taps(nsig, scales, 1e-3, **kw)
         for sc, (h, c) in zip(scales, ref):
             got, gc = route_taps(lib, fam, sc, nsig)
             assert (got.size, gc) == (h.size, c)

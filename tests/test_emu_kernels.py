@@ -6,11 +6,13 @@ import numpy as np
 import pytest
 
 import csd_drive as D
+import cwt_drive as CD
 import emu_driver as E
+import granger_drive as GD
 import jack_oracle as JO
 from oracle import spy_oracle as O
 from parity import assert_parity, excess
-from cwt64_ref import assert_cwt64, cwt64_ref as _cwt64_ref
+from cwt64_ref import assert_cwt64, cwt64_ref as _cwt64_ref, cwt64_taps
 
 
 def _forced_kernel(nfft, generic=False, long=False, no_mixed=False, mixed=False, dec=None):
@@ -402,7 +404,7 @@ def test_cwt_kernel(nsig, scales, detrend, output):
     pre0 = 7                                          # pre-selection starts inside the trial
     ss, lo, hi = np.array([pre0 + 5]), np.array([5]), np.array([5 + nsig + 20])
     scales = np.asarray(scales)
-    out = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, detrend, output, direct=False)[0]
+    out = CD.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, detrend, output, direct=False)[0]
     trial = O.detrend(np.array(data[5:5 + nsig + 20]), None if detrend < 0 else detrend)
     ref = O.convert_output(O.cwt(trial[pre0:pre0 + nsig], 1000.0, scales).transpose(1, 0, 2), output)
     assert_parity(out, ref, what="cwt")
@@ -424,14 +426,14 @@ def test_cwt_direct_kernels(output, nbmin, nchan):
     ref = np.stack([O.convert_output(O.cwt(O.detrend(np.array(data[a:a + nsig]), 0), 1000.0, scales).transpose(1, 0, 2), output)
                     for a in ss])
     trace = []
-    out = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, trace=trace)
+    out = CD.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, trace=trace)
     assert [t.split()[0] for t in trace] == ["cwt_mean_np", "cwt_stage_input", "cwt2d<%d,%d,%d>" % (
         {1024: 10, 2048: 11}[nbmin], {1024: 8, 2048: 4}[nbmin], 2 if output == "fourier" else 0)]
     assert_parity(out, ref, what="direct cwt")
     keep = np.r_[0:3, 5:1300:9, 1023, 1024, 1399]
     tpos = np.full(nsig, -1, dtype=np.int32)
     tpos[keep] = np.arange(keep.size)
-    sel = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=keep.size)
+    sel = CD.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=keep.size)
     assert_parity(sel, ref[:, keep], what="direct cwt, selected samples")
 
 
@@ -451,7 +453,7 @@ def test_cwt_trial_sums_on_pairs_of_trials(output, T):
         ref = sum(O.convert_output(O.cwt(O.detrend(np.array(data[a:a + nsig]), 0), 1000.0, scales).transpose(1, 0, 2).astype(np.complex128), output)
                   for a in ss)[None]
         trace = []
-        out = E.cwt_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, 6.0, 0, output, accumulate=2, trace=trace)
+        out = CD.cwt_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, 6.0, 0, output, accumulate=2, trace=trace)
         assert [t.split()[0] for t in trace if t.startswith("cwt2")] == kernels
         assert_parity(out, ref.astype(out.dtype), what=f"pair sums, {len(kernels)} groups")
 
@@ -468,7 +470,7 @@ def _cwt_plan_case(nsig, freqs_or_scales, nseg, output, accumulate=0, nchan=3, s
     if accumulate == 2:
         ref = ref.astype(np.complex128 if output == "fourier" else np.float64).sum(axis=0, keepdims=True)
     trace = []
-    out = E.cwt_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, 6.0, 0, output, accumulate=accumulate, trace=trace, **kw)
+    out = CD.cwt_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, 6.0, 0, output, accumulate=accumulate, trace=trace, **kw)
     return out, ref.astype(out.dtype), trace
 
 
@@ -544,7 +546,7 @@ def test_cwt64_kernel_outputs_and_detrending(output, detrend):
     data = _cwt64_data(5 + detrend, nsig + 60, nchan)
     ss, lo, hi = np.array([17, 9]), np.array([5, 0]), np.array([5 + nsig + 40, nsig + 30])
     scales = np.array([0.04, 0.012, 0.003])
-    got = E.cwt64_exec(data, ss, lo, hi, nsig, scales, 1e-3, detrend=detrend, output=output)
+    got = CD.cwt64_exec(data, ss, lo, hi, nsig, scales, 1e-3, detrend=detrend, output=output)
     ref = _cwt64_ref(data, ss, lo, hi, nsig, scales, detrend, output)
     if detrend == 1:
         # the line fit is float64 here and float32 lstsq in the reference (VERDICT "What's missing", item 4)
@@ -563,7 +565,7 @@ def test_cwt64_kernel_families(family, order, sl_cycles):
     ss, lo, hi = np.array([3]), np.array([0]), np.array([nsig + 10])
     scales = np.array([0.02, 0.006]) if sl_cycles is None else np.array([0.004, 0.0015])
     for output in ("fourier", "abs"):
-        got = E.cwt64_exec(data, ss, lo, hi, nsig, scales, 1e-3, family=family, order=order, sl_cycles=sl_cycles,
+        got = CD.cwt64_exec(data, ss, lo, hi, nsig, scales, 1e-3, family=family, order=order, sl_cycles=sl_cycles,
                            detrend=0, output=output, chan_idx=ci)
         ref = _cwt64_ref(data, ss, lo, hi, nsig, scales, 0, output, chan_idx=ci, family=family, order=order,
                          sl_cycles=sl_cycles)
@@ -575,18 +577,18 @@ def test_cwt64_kernel_lengths():
     to the taps that overlap it), and nsig + taps - 1 landing exactly on a power of two and one beyond it."""
     data = _cwt64_data(3, 1200, 2)
     cases = [(5, np.array([0.001, 0.0008]), 16), (120, np.array([0.3, 0.05]), None)]
-    taps = E.cwt64_taps(1000, [0.02], 1e-3)[0][0].size
+    taps = cwt64_taps(1000, [0.02], 1e-3)[0][0].size
     assert taps < 500
     cases += [(512 - taps + 1, np.array([0.02, 0.005]), 512), (512 - taps + 2, np.array([0.02, 0.005]), 1024)]
     for nsig, scales, L in cases:
-        Lp = E.cwt_conv_length64(nsig, [h.size for h, _ in E.cwt64_taps(nsig, scales, 1e-3)])
+        Lp = CD.cwt_conv_length64(nsig, [h.size for h, _ in cwt64_taps(nsig, scales, 1e-3)])
         if L is not None:
             assert Lp == L, (nsig, Lp, L)
         else:
-            assert E.cwt64_taps(nsig, scales, 1e-3)[0][0].size < O.cwt_kernel(scales[0], 1e-3).size
+            assert cwt64_taps(nsig, scales, 1e-3)[0][0].size < O.cwt_kernel(scales[0], 1e-3).size
         ss = np.array([40, 0])
         for output in ("fourier", "pow"):
-            got = E.cwt64_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, detrend=0, output=output)
+            got = CD.cwt64_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, detrend=0, output=output)
             ref = _cwt64_ref(data, ss, ss, ss + nsig, nsig, scales, 0, output)
             assert_cwt64(got, ref, output, f"cwt64 nsig {nsig} L {Lp} {output}")
 
@@ -602,9 +604,9 @@ def test_cwt64_kernel_launches_and_chunks(nseg, nchan, chunk):
     scales = np.array([0.01, 0.004])
     for output in ("fourier", "real"):
         ref = _cwt64_ref(data, ss, lo, hi, nsig, scales, 0, output)
-        got = E.cwt64_exec(data, ss, lo, hi, nsig, scales, 1e-3, detrend=0, output=output, per_launch=3, seg_chunk=chunk)
+        got = CD.cwt64_exec(data, ss, lo, hi, nsig, scales, 1e-3, detrend=0, output=output, per_launch=3, seg_chunk=chunk)
         assert_cwt64(got, ref, output, f"cwt64 launches of 3, chunks of {chunk}, {output}")
-        tot = E.cwt64_exec(data, ss, lo, hi, nsig, scales, 1e-3, detrend=0, output=output, per_launch=3, seg_chunk=chunk,
+        tot = CD.cwt64_exec(data, ss, lo, hi, nsig, scales, 1e-3, detrend=0, output=output, per_launch=3, seg_chunk=chunk,
                            accumulate=2)
         r = ref.astype(np.complex128)
         assert_cwt64(tot, r.sum(axis=0, keepdims=True), output, f"cwt64 trial sum, {output}", nterms=nseg,
@@ -624,14 +626,14 @@ def test_cwt64_kernel_selection_and_accumulation(output):
     tpos[keep] = 2 * np.arange(keep.size) + 1                       # odd slots only
     nto = 2 * keep.size + 1
     ref = _cwt64_ref(data, ss, ss, ss + nsig, nsig, scales, 0, output)
-    got = E.cwt64_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, detrend=0, output=output, tpos=tpos, ntime_out=nto)
+    got = CD.cwt64_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, detrend=0, output=output, tpos=tpos, ntime_out=nto)
     assert_cwt64(got[:, 1::2], ref[:, keep], output, f"cwt64 tpos {output}")
     assert not got[:, 0::2].any()
     rng = np.random.default_rng(1)
     base = rng.normal(size=got.shape).astype(got.dtype)
     if output == "fourier":
         base = base + 1j * rng.normal(size=got.shape).astype(np.float32)
-    acc = E.cwt64_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, detrend=0, output=output, tpos=tpos, ntime_out=nto,
+    acc = CD.cwt64_exec(data, ss, ss, ss + nsig, nsig, scales, 1e-3, detrend=0, output=output, tpos=tpos, ntime_out=nto,
                        accumulate=1, out=base.copy(), seg_chunk=1)
     assert np.array_equal(acc[:, 0::2], base[:, 0::2])
     b = base[:, 1::2].astype(np.complex128)
@@ -646,7 +648,7 @@ def test_cwt64_kernel_wide_transposition():
     ss = np.array([4])
     scales = np.array([0.006])
     for output, acc in (("pow", 0), ("imag", 2)):
-        got = E.cwt64_exec(data, ss, ss - 4, ss + nsig + 4, nsig, scales, 1e-3, detrend=0, output=output, accumulate=acc)
+        got = CD.cwt64_exec(data, ss, ss - 4, ss + nsig + 4, nsig, scales, 1e-3, detrend=0, output=output, accumulate=acc)
         ref = _cwt64_ref(data, ss, ss - 4, ss + nsig + 4, nsig, scales, 0, output)
         assert_cwt64(got, ref, output, f"cwt64 wide transposition {output}")
 
@@ -658,33 +660,33 @@ def test_cwt_direct_bound():
     # contiguous slots: the span of a full block is V - 1; a ragged last block spans less
     V, chanb = 1000, 256
     rowb = (lim - chanb) // 999
-    assert E.cwt_direct_fits(None, 5000, [V], rowb, chanb)
-    assert not E.cwt_direct_fits(None, 5000, [V], rowb + 1, chanb)
-    assert E.cwt_direct_fits(None, 1500, [V], rowb, chanb)                # (the ragged last tile spans 499)
-    assert not E.cwt_direct_fits(None, 1500, [2000], rowb, chanb)         # one tile of 1500 samples spans 1499
-    assert E.cwt_direct_fits(None, 1500, [2000], (lim - chanb) // 1499, chanb)
+    assert CD.cwt_direct_fits(None, 5000, [V], rowb, chanb)
+    assert not CD.cwt_direct_fits(None, 5000, [V], rowb + 1, chanb)
+    assert CD.cwt_direct_fits(None, 1500, [V], rowb, chanb)                # (the ragged last tile spans 499)
+    assert not CD.cwt_direct_fits(None, 1500, [2000], rowb, chanb)         # one tile of 1500 samples spans 1499
+    assert CD.cwt_direct_fits(None, 1500, [2000], (lim - chanb) // 1499, chanb)
     # gapped slots tpos[n] = 10000 n: a 1004-sample tile spans 10 030 000 slots
     tp = (10000 * np.arange(2048)).astype(np.int32)
-    assert E.cwt_direct_fits(tp, 2048, [1004], 256, 32)                   # 2.57e9 bytes
-    assert not E.cwt_direct_fits(tp, 2048, [1004], 512, 64)               # 5.14e9 bytes
-    assert not E.cwt_direct_fits(tp, 2048, [2000, 1004], 256, 32)         # a second group with longer tiles
+    assert CD.cwt_direct_fits(tp, 2048, [1004], 256, 32)                   # 2.57e9 bytes
+    assert not CD.cwt_direct_fits(tp, 2048, [1004], 512, 64)               # 5.14e9 bytes
+    assert not CD.cwt_direct_fits(tp, 2048, [2000, 1004], 256, 32)         # a second group with longer tiles
     span = 10000 * 1003
-    assert E.cwt_direct_fits(tp, 2048, [1004], (lim - 64) // span, 64)
-    assert not E.cwt_direct_fits(tp, 2048, [1004], (lim - 64) // span + 1, 64)
+    assert CD.cwt_direct_fits(tp, 2048, [1004], (lim - 64) // span, 64)
+    assert not CD.cwt_direct_fits(tp, 2048, [1004], (lim - 64) // span + 1, 64)
     # unmapped samples: the tile's reference is the slot reached before it (0 before any) - the second tile [1004, 2008)
     # spans 4e6 + 507 * 10000 slots from slot 0 though only its last 508 samples are mapped
     tq = np.full(2048, -1, dtype=np.int32)
     tq[1500:] = 10000 * np.arange(548) + 4000000
-    assert not E.cwt_direct_fits(tq, 2048, [1004], 512, 64)
-    assert E.cwt_direct_fits(tq, 2048, [1004], 256, 32)
+    assert not CD.cwt_direct_fits(tq, 2048, [1004], 512, 64)
+    assert CD.cwt_direct_fits(tq, 2048, [1004], 256, 32)
     tq[1500:] -= 4000000 - 5000
-    assert E.cwt_direct_fits(tq, 2048, [1004], 512, 64)
+    assert CD.cwt_direct_fits(tq, 2048, [1004], 512, 64)
     # slots not increasing
-    assert not E.cwt_direct_fits(np.r_[0, 2, 1].astype(np.int32), 3, [1004], 8, 8)
-    assert not E.cwt_direct_fits(np.r_[0, 1, 1].astype(np.int32), 3, [1004], 8, 8)
-    assert E.cwt_direct_fits(np.r_[0, -1, 1].astype(np.int32), 3, [1004], 8, 8)
+    assert not CD.cwt_direct_fits(np.r_[0, 2, 1].astype(np.int32), 3, [1004], 8, 8)
+    assert not CD.cwt_direct_fits(np.r_[0, 1, 1].astype(np.int32), 3, [1004], 8, 8)
+    assert CD.cwt_direct_fits(np.r_[0, -1, 1].astype(np.int32), 3, [1004], 8, 8)
     # production shape (c4: 128 channels, 25 scales, complex): nowhere near
-    assert E.cwt_direct_fits(None, 16384, [1004, 1900], 25 * 128 * 8, 128 * 8)
+    assert CD.cwt_direct_fits(None, 16384, [1004, 1900], 25 * 128 * 8, 128 * 8)
 
 
 @pytest.mark.parametrize("output", ["pow", "fourier"])
@@ -701,13 +703,13 @@ def test_cwt_direct_kernels_gapped_slots(output):
     nto = 7 * nsig + 5
     ref = np.stack([O.convert_output(O.cwt(O.detrend(np.array(data[a:a + nsig]), 0), 1000.0, scales).transpose(1, 0, 2), output)
                     for a in ss])
-    out = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=nto)
+    out = CD.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=nto)
     assert_parity(out[:, tpos], ref, what="direct cwt, gapped slots")
     gap = np.ones(nto, dtype=bool)
     gap[tpos] = False
     assert not out[:, gap].any()
     base = np.full(out.shape, 0.25, dtype=out.dtype)
-    acc = E.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=nto,
+    acc = CD.cwt_exec(data, ss, lo, hi, nsig, scales, 1e-3, 6.0, 0, output, tpos=tpos, ntime_out=nto,
                      accumulate=1, out=base.copy())
     assert np.array_equal(acc[:, gap], base[:, gap])
     assert_parity(acc[:, tpos] - base[:, tpos], ref, what="direct cwt, gapped slots, accumulate 1")
@@ -721,12 +723,12 @@ def test_blocked_inverse(n):
     B = 2
     A = rng.normal(size=(B, n, n)) + 1j * rng.normal(size=(B, n, n)) + 3 * np.sqrt(n) * np.eye(n)
     kw = dict(blocked=True, lds_per_block=64 * 1024, kernel="spywil::zinv_blocked_kernel")
-    inv, info = E.w_inv(A, **kw)
+    inv, info = GD.inv(A, **kw)
     assert not info.any()
     np.testing.assert_allclose(inv @ A, np.tile(np.eye(n), (B, 1, 1)), atol=1e-10)
     P = np.zeros((1, n, n), complex)
     P[0] = np.eye(n)[::-1]                     # anti-diagonal permutation: every leading block is singular
-    _, info = E.w_inv(P, **kw)
+    _, info = GD.inv(P, **kw)
     assert info[0] == 2
 
 
@@ -738,12 +740,12 @@ def test_blocked_inverse_on_f64_matrix_cores(n):
     rng = np.random.default_rng(n)
     B = 2
     A = rng.normal(size=(B, n, n)) + 1j * rng.normal(size=(B, n, n)) + 3 * np.sqrt(n) * np.eye(n)
-    inv, info = E.w_inv(A, blocked=True, kernel="spywil::zinv_mfma_kernel")
+    inv, info = GD.inv(A, blocked=True, kernel="spywil::zinv_mfma_kernel")
     assert not info.any()
     np.testing.assert_allclose(inv, np.linalg.inv(A), rtol=1e-9, atol=1e-11)
     P = np.zeros((1, n, n), complex)
     P[0] = np.eye(n)[::-1]
-    _, info = E.w_inv(P, blocked=True, kernel="spywil::zinv_mfma_kernel")
+    _, info = GD.inv(P, blocked=True, kernel="spywil::zinv_mfma_kernel")
     assert info[0] == 2
 
 
@@ -756,12 +758,12 @@ def test_blocked_inverse_with_64_row_blocks(n):
     rng = np.random.default_rng(n)
     B = 1 if n > 128 else 2            # (one OS thread per GPU thread: 192 x 192 costs 20 s per matrix)
     A = rng.normal(size=(B, n, n)) + 1j * rng.normal(size=(B, n, n)) + 3 * np.sqrt(n) * np.eye(n)
-    inv, info = E.w_inv(A, blocked=True, kernel="spywil::zinv64_mfma_kernel")
+    inv, info = GD.inv(A, blocked=True, kernel="spywil::zinv64_mfma_kernel")
     assert not info.any()
     np.testing.assert_allclose(inv, np.linalg.inv(A), rtol=1e-9, atol=1e-11)
     P = np.zeros((1, n, n), complex)
     P[0] = np.eye(n)[::-1]
-    _, info = E.w_inv(P, blocked=True, kernel="spywil::zinv64_mfma_kernel")
+    _, info = GD.inv(P, blocked=True, kernel="spywil::zinv64_mfma_kernel")
     assert info[0] == 2
 
 
@@ -774,7 +776,7 @@ def test_plus_operator(F):
     full[:F] = g
     full[F:] = np.conj(g[1:F - 1][::-1])
     ref, ref0 = O.plus_operator(full)
-    gp, g0 = E.w_plus(g, kernel="spywil::plus_kernel")
+    gp, g0 = GD.plus(g, kernel="spywil::plus_kernel")
     np.testing.assert_allclose(gp, ref[:F], rtol=1e-12, atol=1e-12)
     np.testing.assert_allclose(g0, ref0, rtol=1e-12, atol=1e-12)
 
@@ -791,10 +793,10 @@ def test_plus_operator_two_entries_per_transform(F, n):
     full[:F] = g
     full[F:] = np.conj(g[1:F - 1][::-1])
     ref, ref0 = O.plus_operator(full)
-    gp, g0 = E.w_plus(g, kernel="spywil::plus4_kernel<%d>" % (L.bit_length() - 1))
+    gp, g0 = GD.plus(g, kernel="spywil::plus4_kernel<%d>" % (L.bit_length() - 1))
     np.testing.assert_allclose(gp, ref[:F], rtol=1e-12, atol=1e-12)
     np.testing.assert_allclose(g0, ref0, rtol=1e-12, atol=1e-12)
-    old, old0 = E.w_plus(g, generic=True, kernel="spywil::plus_kernel")
+    old, old0 = GD.plus(g, generic=True, kernel="spywil::plus_kernel")
     np.testing.assert_allclose(gp, old, rtol=1e-12, atol=1e-12)
 
 
@@ -805,14 +807,14 @@ def test_zgemm_on_f64_matrix_cores():
     n = 50
     A = rng.normal(size=(1, n, n)) + 1j * rng.normal(size=(1, n, n))
     Bm = rng.normal(size=(1, n, n)) + 1j * rng.normal(size=(1, n, n))
-    np.testing.assert_allclose(E.w_gemm(A, Bm, kernel="spywil::zgemm_mfma_kernel<0>"), A @ Bm, rtol=1e-12, atol=1e-12)
-    np.testing.assert_allclose(E.w_gemm(A, Bm, opB=1, addI=1), A @ Bm.conj().transpose(0, 2, 1) + np.eye(n), rtol=1e-12,
+    np.testing.assert_allclose(GD.gemm(A, Bm, kernel="spywil::zgemm_mfma_kernel<0>"), A @ Bm, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(GD.gemm(A, Bm, opB=1, addI=1), A @ Bm.conj().transpose(0, 2, 1) + np.eye(n), rtol=1e-12,
                                atol=1e-12)
     # addI & 2: B declared lower triangular (the Cholesky factor): the zero rows above a column tile are skipped
     n = 130
     A = rng.normal(size=(1, n, n)) + 1j * rng.normal(size=(1, n, n))
     L = np.tril(rng.normal(size=(1, n, n)) + 1j * rng.normal(size=(1, n, n)))
-    np.testing.assert_allclose(E.w_gemm(A, L, addI=2), A @ L, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(GD.gemm(A, L, addI=2), A @ L, rtol=1e-12, atol=1e-12)
 
 
 def test_zgemm_fused_skew_and_error_check():
@@ -824,17 +826,17 @@ def test_zgemm_fused_skew_and_error_check():
     psi = rng.normal(size=(B, n, n)) + 1j * rng.normal(size=(B, n, n))
     gp = rng.normal(size=(B, n, n)) + 1j * rng.normal(size=(B, n, n))
     g0 = rng.normal(size=(n, n)) + 1j * rng.normal(size=(n, n))
-    S, g0S = E.w_skew(g0)
+    S, g0S = GD.skew(g0)
     Sref = np.triu(g0) - np.triu(g0).conj().T
     np.testing.assert_allclose(S, Sref, rtol=0, atol=0)
     np.testing.assert_allclose(g0S, g0 + Sref, rtol=1e-15)
-    np.testing.assert_allclose(E.w_gemm(psi, gp, badd=S, kernel="spywil::zgemm_mfma_kernel<1>"), psi @ (gp + Sref), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(GD.gemm(psi, gp, badd=S, kernel="spywil::zgemm_mfma_kernel<1>"), psi @ (gp + Sref), rtol=1e-12, atol=1e-12)
     # X X^H + I through the Hermitian instance (lower tiles computed, mirrored above the diagonal)
-    np.testing.assert_allclose(E.w_gemm(psi, psi, opB=1, addI=1, kernel="spywil::zgemm_mfma_kernel<3>"),
+    np.testing.assert_allclose(GD.gemm(psi, psi, opB=1, addI=1, kernel="spywil::zgemm_mfma_kernel<3>"),
                                psi @ psi.conj().transpose(0, 2, 1) + np.eye(n), rtol=1e-12, atol=1e-12)
     herm = rng.normal(size=(B, n, n)) * 1e-3
     ref = psi @ psi.conj().transpose(0, 2, 1) * (1 + herm + herm.transpose(0, 2, 1))        # Hermitian reference
-    err = E.w_gemm(psi, psi, opB=1, ref=ref, kernel="spywil::zgemm_mfma_kernel<2>")
+    err = GD.gemm(psi, psi, opB=1, ref=ref, kernel="spywil::zgemm_mfma_kernel<2>")
     np.testing.assert_allclose(err, O.max_rel_err(ref, psi @ psi.conj().transpose(0, 2, 1)), rtol=1e-10)
 
 
@@ -844,7 +846,7 @@ def test_hermitian_zgemm_ragged_tiles(n):
     tile row whose mirror fills the column above it (65); nine matrices, so the batch is not a multiple of 8."""
     rng = np.random.default_rng(n)
     X = rng.normal(size=(9, n, n)) + 1j * rng.normal(size=(9, n, n))
-    np.testing.assert_allclose(E.w_gemm(X, X, opB=1, addI=1, kernel="spywil::zgemm_mfma_kernel<3>"),
+    np.testing.assert_allclose(GD.gemm(X, X, opB=1, addI=1, kernel="spywil::zgemm_mfma_kernel<3>"),
                                X @ X.conj().transpose(0, 2, 1) + np.eye(n), rtol=1e-12, atol=1e-12)
 
 
@@ -853,18 +855,18 @@ def test_wilson_building_blocks():
     n, B = 37, 3
     A = rng.normal(size=(B, n, n)) + 1j * rng.normal(size=(B, n, n))
     Bm = rng.normal(size=(B, n, n)) + 1j * rng.normal(size=(B, n, n))
-    np.testing.assert_allclose(E.w_gemm(A, Bm), A @ Bm, rtol=1e-12, atol=1e-12)
-    np.testing.assert_allclose(E.w_gemm(A, Bm, opB=1, addI=1), A @ Bm.conj().transpose(0, 2, 1) + np.eye(n), rtol=1e-12,
+    np.testing.assert_allclose(GD.gemm(A, Bm), A @ Bm, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(GD.gemm(A, Bm, opB=1, addI=1), A @ Bm.conj().transpose(0, 2, 1) + np.eye(n), rtol=1e-12,
                                atol=1e-12)
-    np.testing.assert_allclose(E.w_gemm(A, Bm[0], kernel="spywil::zgemm_kernel"), A @ Bm[0], rtol=1e-12, atol=1e-12)        # broadcast B
-    inv, info = E.w_inv(A, kernel="spywil::zinv_kernel")
+    np.testing.assert_allclose(GD.gemm(A, Bm[0], kernel="spywil::zgemm_kernel"), A @ Bm[0], rtol=1e-12, atol=1e-12)        # broadcast B
+    inv, info = GD.inv(A, kernel="spywil::zinv_kernel")
     assert not info.any()
     np.testing.assert_allclose(inv @ A, np.tile(np.eye(n), (B, 1, 1)), atol=1e-9)
     P = A @ A.conj().transpose(0, 2, 1) + n * np.eye(n)
-    Lc, info = E.w_chol(P, kernel="spywil::zchol_kernel")
+    Lc, info = GD.chol(P, kernel="spywil::zchol_kernel")
     assert not info.any()
     np.testing.assert_allclose(Lc, np.linalg.cholesky(P), rtol=1e-10, atol=1e-10)
-    assert abs(E.w_cond(P[:1, :9, :9].copy(), iters=40) / np.linalg.cond(P[0, :9, :9]) - 1) < 5e-2
+    assert abs(GD.cond(P[:1, :9, :9]) / np.linalg.cond(P[0, :9, :9]) - 1) < 5e-2
 
 
 @pytest.mark.parametrize("n", [64, 70])
@@ -875,7 +877,7 @@ def test_panel_cholesky(n):
     X = rng.normal(size=(3, n, n)) + 1j * rng.normal(size=(3, n, n))
     P = X @ X.conj().transpose(0, 2, 1) + 0.5 * n * np.eye(n)
     P[2, 40, 40] = -1.0                                        # third matrix: indefinite
-    Lc, info = E.w_chol(P, kernel="spywil::zchol_panel_kernel")
+    Lc, info = GD.chol(P, kernel="spywil::zchol_panel_kernel")
     assert list(info) == [0, 0, 1]
     np.testing.assert_allclose(Lc[:2], np.linalg.cholesky(P[:2]), rtol=1e-10, atol=1e-10)
     assert np.all(np.triu(Lc[:2], 1) == 0)
@@ -894,10 +896,10 @@ def test_wilson_granger_small_vs_oracle():
         cs, _ = O.csd(O.detrend(x, 0), 200.0, 32, "dpss", {"NW": 2, "Kmax": 3}, demean_taper=True)
         acc += cs
     acc /= len(trials)
-    G, H, Sigma, info = E.granger(acc, cond_iters=25)
+    G, H, Sigma, info = GD.granger(acc)
     Gr, meta = O.granger_cF(acc[None])
     assert bool(info[0]) == bool(meta["converged--bool"]) and info[2] == float(meta["reg. factor--float"])
-    np.testing.assert_allclose(info[3], float(meta["initial cond. num--float"]), rtol=0.2)   # 25 power iterations only
+    np.testing.assert_allclose(info[3], float(meta["initial cond. num--float"]), rtol=0.2)
     assert info[1] < 5e-6
     rec = H @ Sigma @ H.conj().transpose(0, 2, 1)
     assert O.max_rel_err(acc.astype(np.complex128), rec) < 1e-5

@@ -1,7 +1,7 @@
 """Which kernels serve the Wilson / Granger stage (K6), with which grid and LDS, and where the work arrays of
 spyhip_granger lie: the pure route of syncopy_amd/csrc/granger_route.h, compiled with the host compiler alone (no HIP, no
-device) and asked through a small C shim (tests/emu/granger_route_shim.cpp).  granger.hip and the kernel emulator both
-launch by this header.
+device) and asked through a small C shim (tests/emu/granger_route_shim.cpp).  granger.hip launches by this
+header, and the kernel emulator runs granger.hip (tests/emu/granger_emu.cpp).
 
 The size classes at the 160 KiB of LDS per workgroup of the MI355X (ZB = 16, ZM = 32, ZW = 64, CHP = 32, MT = 64):
 
