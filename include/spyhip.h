@@ -322,6 +322,34 @@ int spyhip_phaselag_finalize(spyhip_ctx* ctx, const void* acc_d, int nfreq, int 
 int spyhip_plv_finalize(spyhip_ctx* ctx, const void* acc_d, int nfreq, int ni, int nj, int lower_only,
                         int64_t ntrials, void* out_d);
 
+/* ---- K12: envelope correlations - amplitude, power, orthogonalised power ------
+ * Not in the reference (Hipp et al. 2012).  Over the R = ntrials x ntaper repetitions r = (trial, taper) of the tapered
+ * spectra x_i(r) of one frequency - every taper is a repetition, nothing is summed over tapers - and with
+ *   corr(X; E1a, E2a, E1b, E2b) = (X - E1a E1b / R) / sqrt(va vb),  va = E2a - E1a^2 / R,  vb = E2b - E1b^2 / R,
+ *   0 (not NaN) where a variance is zero, which is v <= 2^-40 E2:
+ *   amplcorr (e = |x|), powcorr (e = |x|^2):  corr(sum e_i e_j; sum e_i, sum e_i^2, sum e_j, sum e_j^2);
+ *   powcorr_ortho:  p = |x|^2,  s = Im(x_i conj(x_j)),  q_j|i = s^2 / p_i (0 where p_i = 0),  Z = sum s^2,
+ *     c_j|i = corr(Z; sum p_i, sum p_i^2, sum q_j|i, sum q_j|i^2),  result (c_j|i + c_i|j) / 2, 0 unless both exist.
+ *   |x|, p, 1 / p, s, s^2 and q are float32; their products and every sum are float64.  No spectral normalisation is
+ *   needed: a positive scale per channel changes no result.
+ * spyhip_envcorr_accumulate: the sums of the batch straight from the tapered spectra (spec_d as for
+ *   spyhip_ppc_accumulate).  pair_d float64 (NP, nfreq, nchan, nchan), planar, NP = 1 {sum e_i e_j} for amplcorr and
+ *   powcorr, NP = 5 {Z, sum q_j|i, sum q_j|i^2, sum q_i|j, sum q_i|j^2} at [i, j] for powcorr_ortho, maintained on the
+ *   lower triangle (32x32 tile granularity); chan_d float64 (nfreq, nchan, 2) {sum e, sum e^2}, for powcorr_ortho
+ *   {sum p, sum p^2}.  Both zeroed by the caller; plain sums, so ranks are combined by one sum each.  ntrials = 0 does
+ *   nothing.  -3: the tapers do not fit the LDS: the two staging buffers take 1 KiB per taper for amplcorr and powcorr
+ *   (160 tapers in 160 KiB, as K7 and K10) and 2 KiB per taper for powcorr_ortho (80 tapers).
+ * spyhip_envcorr_finalize: out float32 (nfreq, nchan, nchan) for `measure` from the two accumulators and the total
+ *   number of repetitions nrep (at least 2), evaluated in float64, clamped to [-1, 1] and rounded once; the upper
+ *   triangle is mirrored; the diagonal is exact: 1 where the channel's variance is not zero and 0 elsewhere for amplcorr
+ *   and powcorr, 0 for powcorr_ortho.
+ * -1: a null or non-positive argument, an unknown measure, nrep < 2. */
+enum { SPYHIP_ENVCORR_AMPL = 0, SPYHIP_ENVCORR_POW = 1, SPYHIP_ENVCORR_POW_ORTHO = 2 };
+int spyhip_envcorr_accumulate(spyhip_ctx* ctx, const void* spec_d, int ntrials, int ntaper, int nfreq, int nchan,
+                              int measure, void* pair_d, void* chan_d);
+int spyhip_envcorr_finalize(spyhip_ctx* ctx, const void* pair_d, const void* chan_d, int nfreq, int nchan, int64_t nrep,
+                            int measure, void* out_d);
+
 /* ---- K9: streaming jackknife of the coherence --------------------------------
  * Replaces, for method='coh' with jackknife=True, the T leave-one-out trial averages (statistics/jackknifing.py:14-108),
  * the AV stage on every replicate (connectivity_analysis.py:736-745) and the sums behind bias_var (:111-184):

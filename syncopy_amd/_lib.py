@@ -67,6 +67,8 @@ SIGNATURES = {
     "spyhip_phaselag_accumulate_csd": (C.c_int, [vp, vp, C.c_int, C.c_int64, vp]),
     "spyhip_phaselag_finalize": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, vp]),
     "spyhip_plv_finalize": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
+    "spyhip_envcorr_accumulate": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "spyhip_envcorr_finalize": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int64, C.c_int, vp]),
     "spyhip_jack_coh_accumulate": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int64,
                                              vp, vp]),
     "spyhip_ccov_nfft": (C.c_int, [C.c_int]),

@@ -30,6 +30,7 @@ OUTPUT_KIND = {"pow": 0, "abs": 1, "fourier": 2, "complex": 2, "real": 3, "imag"
                "absreal": 6, "absimag": 7}
 DETREND = {None: -1, False: -1, 0: 0, 1: 1}
 PHASELAG_MEASURE = {"pli": 0, "wpli": 1, "wpli_debiased": 2}       # SPYHIP_PHASELAG_* (include/spyhip.h)
+ENVCORR_MEASURE = {"amplcorr": 0, "powcorr": 1, "powcorr_ortho": 2}  # SPYHIP_ENVCORR_*
 
 
 class Buffer:
@@ -277,6 +278,34 @@ class Device:
             for b in (md, wd, out):
                 if b is not None:
                     b.free()
+
+    # ---- K1 + K12
+    def envelope_measure(self, queue, tapers, scale, nfft=None, detrend=0, method="powcorr_ortho", nrep_total=None):
+        """connectivityanalysis(method='amplcorr' | 'powcorr' | 'powcorr_ortho'): (F, C, C) float32.  The sums over the
+        repetitions (trial x taper) of this rank's trials are summed over ranks if a communicator exists (`nrep_total`:
+        all ranks' repetitions)."""
+        if method not in ENVCORR_MEASURE:
+            raise ValueError(f"no envelope measure {method!r}")
+        spec = self.mtmfft(queue, tapers, scale, nfft, detrend, False, None, "fourier", True, device_result=True)
+        T, K, F, Cn = spec.shape
+        measure = ENVCORR_MEASURE[method]
+        pair = Buffer(self, (5 if method == "powcorr_ortho" else 1, F, Cn, Cn), np.float64, zero=True)
+        chan = Buffer(self, (F, Cn, 2), np.float64, zero=True)
+        check(self.lib.spyhip_envcorr_accumulate(self.handle, spec.ptr, T, K, F, Cn, measure, pair.ptr, chan.ptr),
+              "spyhip_envcorr_accumulate")
+        self.synchronize()
+        spec.free()
+        if self.has_comm:
+            for acc in (pair, chan):
+                check(self.lib.spyhip_allreduce(self.handle, acc.ptr, int(np.prod(acc.shape)), 1), "spyhip_allreduce")
+        nrep = T * K if nrep_total is None else int(nrep_total)
+        out = Buffer(self, (F, Cn, Cn), np.float32)
+        check(self.lib.spyhip_envcorr_finalize(self.handle, pair.ptr, chan.ptr, F, Cn, nrep, measure, out.ptr),
+              "spyhip_envcorr_finalize")
+        res = out.numpy()
+        for b in (out, pair, chan):
+            b.free()
+        return res
 
     # ---- spy.timelockanalysis
     def cov(self, trials, ddof=None):

@@ -1037,6 +1037,53 @@ def phase_accumulator(method, shape, device):
             lambda a, ntrials, lower_only: phaselag_finalize(a, ntrials, lower_only, method))
 
 
+ENVCORR_MEASURE = {"amplcorr": 0, "powcorr": 1, "powcorr_ortho": 2}     # SPYHIP_ENVCORR_* (include/spyhip.h)
+ENVCORR_PLANES = {"amplcorr": 1, "powcorr": 1, "powcorr_ortho": 5}
+
+
+def envcorr_accumulate(spec, ntaper, pair, chan, measure):
+    """pair (NP, F, C, C) and chan (F, C, 2) float64 += the sums over the repetitions (trial x taper) of tapered spectra
+    spec (ntrials * ntaper, F, C) complex64 that the envelope correlation `measure` needs (K12; lower triangle maintained)."""
+    assert spec.is_cuda and spec.dtype == torch.complex64 and spec.is_contiguous() and spec.dim() == 3
+    assert pair.is_cuda and pair.dtype == torch.float64 and pair.is_contiguous()
+    assert chan.is_cuda and chan.dtype == torch.float64 and chan.is_contiguous()
+    R, F, Cn = spec.shape
+    assert R % ntaper == 0 and tuple(pair.shape) == (ENVCORR_PLANES[measure], F, Cn, Cn) and tuple(chan.shape) == (F, Cn, 2)
+    ctx = context(spec.device)
+    ctx.bind_stream()
+    check(ctx.lib.spyhip_envcorr_accumulate(ctx.handle, _ptr(spec), R // ntaper, int(ntaper), F, Cn, ENVCORR_MEASURE[measure],
+                                            _ptr(pair), _ptr(chan)), "spyhip_envcorr_accumulate")
+
+
+def envcorr_finalize(pair, chan, nrep, measure):
+    """'amplcorr' | 'powcorr' | 'powcorr_ortho' (F, C, C) float32 from the accumulated sums of `nrep` repetitions."""
+    assert pair.is_cuda and pair.dtype == torch.float64 and pair.is_contiguous() and pair.dim() == 4
+    assert chan.is_cuda and chan.dtype == torch.float64 and chan.is_contiguous()
+    NP, F, Cn, _ = pair.shape
+    assert NP == ENVCORR_PLANES[measure] and pair.shape[3] == Cn and tuple(chan.shape) == (F, Cn, 2)
+    out = torch.empty((F, Cn, Cn), dtype=torch.float32, device=pair.device)
+    ctx = context(pair.device)
+    ctx.bind_stream()
+    check(ctx.lib.spyhip_envcorr_finalize(ctx.handle, _ptr(pair), _ptr(chan), F, Cn, int(nrep), ENVCORR_MEASURE[measure],
+                                          _ptr(out)), "spyhip_envcorr_finalize")
+    return out
+
+
+def envelope_accumulator(method, shape, device):
+    """the zeroed accumulators of an envelope correlation over `shape` = (F, C), how to add a batch of tapered spectra to
+    them and how to finish them (K12).  Returns ((pair, chan), accumulate(spec, ntaper, pair, chan),
+    finalize(pair, chan, nrep)) with nrep the number of repetitions (trials x tapers) of all ranks; both accumulators are
+    plain sums.  pair is float64 (NP, F, C, C): 1.07 GB at 256 channels x 2049 frequencies for 'amplcorr' and 'powcorr'
+    (NP = 1), 5.4 GB for 'powcorr_ortho' (NP = 5)."""
+    if method not in ENVCORR_MEASURE:
+        raise ValueError(f"no envelope measure {method!r}")
+    F, Cn = shape
+    pair = torch.zeros((ENVCORR_PLANES[method], F, Cn, Cn), dtype=torch.float64, device=device)
+    chan = torch.zeros((F, Cn, 2), dtype=torch.float64, device=device)
+    return ((pair, chan), lambda spec, ntaper, p, c: envcorr_accumulate(spec, ntaper, p, c, method),
+            lambda p, c, nrep: envcorr_finalize(p, c, nrep, method))
+
+
 def jack_coh_accumulate(spec, ntaper, csd, direct, output, ntrials_total, sum_d, sum_d2):
     """Streaming jackknife of the coherence (K9): for every trial of spec (ntrials * ntaper, F, C) the leave-one-out
     coherence replicate minus `direct` is summed into sum_d (float64 / complex128) and its squared modulus into

@@ -10,7 +10,7 @@ import torch
 from .. import backend, parallel
 from ..datatype import device_rows, selected_channels, trial_rows
 from ..shared.computational_routine import ComputationalRoutine, propagate_properties
-from ..shared.const_def import phaseMethods, spectralDTypes
+from ..shared.const_def import envelopeMethods, phaseMethods, spectralDTypes
 from ..shared.errors import SPYValueError
 from ..shared.tools import best_match
 from ..specest import hip_spectral as hs
@@ -122,6 +122,36 @@ def _cmb_block(acc, sub):
     return acc.index_select(-2, si).index_select(-1, ri).contiguous()
 
 
+def _trial_stream_sums(measure, F, C, device):
+    """What the two `ppc_hip` methods keep of the stream of tapered spectra for `measure`: (add(spec, ntaper),
+    finish(ntrials) -> (F, C, C) float32 on the device).  K7's or K10's one accumulator (backend.phase_accumulator), or the
+    two of an envelope correlation (K12: backend.envelope_accumulator), whose count is the repetitions - trials x tapers -
+    and not the trials.  `finish` sums every accumulator over the ranks first."""
+    if measure in envelopeMethods:
+        accs, accumulate, finalize = backend.envelope_accumulator(measure, (F, C), device)
+        nrep = [0]
+
+        def add(spec, ntaper):
+            accumulate(spec, ntaper, *accs)
+            nrep[0] += spec.shape[0]
+
+        def finish(ntrials):
+            total = torch.tensor([nrep[0]], dtype=torch.float64, device=device)
+            for a in accs + (total,):
+                parallel.allreduce_sum_(a)
+            return finalize(*accs, int(total.item()))
+        return add, finish
+    U, accumulate, _, finalize = backend.phase_accumulator(measure, (F, C, C), device)
+
+    def add(spec, ntaper):
+        accumulate(spec, ntaper, U)
+
+    def finish(ntrials):
+        parallel.allreduce_sum_(U)
+        return finalize(U, ntrials, lower_only=True)
+    return add, finish
+
+
 class SpectralDyadicProduct(ComputationalRoutine):
     """CrossSpectra's sibling for SpectralData input (`freqanalysis(output="fourier", keeptapers=True)` chained into
     `connectivityanalysis`): nothing but K4 on spectra that already exist."""
@@ -168,8 +198,8 @@ class SpectralDyadicProduct(ComputationalRoutine):
         every time sample (time-resolved spectra: all trials must have the same number of samples, as the reference's
         accumulator `st_out.trials[0].shape` requires, connectivity_analysis.py:626); `channelcmb` rectangles are
         cut out of the channels that occur at all.  `measure`: 'ppc', or one of its siblings 'plv' (K7's sums, another
-        finalizer), 'pli', 'wpli', 'wpli_debiased' (K10: backend.phase_accumulator).  Returns (nTime, F, C_i, C_j) on the
-        device."""
+        finalizer), 'pli', 'wpli', 'wpli_debiased' (K10: backend.phase_accumulator), or an envelope correlation 'amplcorr',
+        'powcorr', 'powcorr_ortho' (K12: backend.envelope_accumulator).  Returns (nTime, F, C_i, C_j) on the device."""
         rows, chans = trial_rows(data), selected_channels(data)
         T = self.numTrials
         lens = {rows[k][1] - rows[k][0] for k in range(T)}
@@ -188,12 +218,11 @@ class SpectralDyadicProduct(ComputationalRoutine):
         first = np.array([rows[k][0] for k in mine], dtype=np.int64)
         res = []
         for ti in range(L):
-            U, accumulate, _, finalize = backend.phase_accumulator(measure, (F, C, C), "cuda")
+            add, finish = _trial_stream_sums(measure, F, C, "cuda")
             if len(mine):
                 dev = torch.from_numpy(np.ascontiguousarray(host[first + ti], dtype=np.complex64)).cuda()
-                accumulate(dev.reshape(-1, F, C), K, U)
-            parallel.allreduce_sum_(U)
-            r = finalize(U, T, lower_only=True)
+                add(dev.reshape(-1, F, C), K)
+            r = finish(T)
             res.append(r if sub is None else _cmb_block(r, sub))
         return torch.stack(res, dim=0)
 
@@ -332,7 +361,10 @@ class CrossSpectra(ComputationalRoutine):
         cross spectrum, normalises it to a unit phasor and sums over trials in registers; one sum over ranks, then
         ppc = (|U|^2 - T)/(T(T-1)).  No single-trial cross spectrum is ever stored (the reference keeps all T of them
         and visits T(T-1)/2 pairs).  `measure`: 'ppc', or one of its siblings 'plv' (the same sums, |U| / T), 'pli', 'wpli',
-        'wpli_debiased' (K10 on the same stream: backend.phase_accumulator).  Returns the (F, C, C) float32 device tensor."""
+        'wpli_debiased' (K10 on the same stream: backend.phase_accumulator), or an envelope correlation 'amplcorr', 'powcorr',
+        'powcorr_ortho' (K12 on the same stream, every taper a repetition: backend.envelope_accumulator; its pair sums are
+        float64, 1.07 GB at 256 channels x 2049 frequencies and 5.4 GB for 'powcorr_ortho').  Returns the (F, C, C) float32
+        device tensor."""
         cfg = self.cfg
         dev = data.device_data()
         rows, chans = device_rows(data), selected_channels(data)
@@ -342,13 +374,12 @@ class CrossSpectra(ComputationalRoutine):
         F, C = self.targetShapes[0][1], self.targetShapes[0][2]
         T = self.numTrials
         mine = [rows[k] for k in self.my_trials()]
-        U, accumulate, _, finalize = backend.phase_accumulator(measure, (F, C, C), dev.device)
+        add, finish = _trial_stream_sums(measure, F, C, dev.device)
         for _, spec in hs.run_mtmfft_batches(dev, mine, chans, cfg["nSamples"], cfg["taper"], cfg["taper_opt"],
                                              cfg["demean_taper"], False, pr, freq_idx, "fourier", True, reuse=True):
-            accumulate(spec.reshape(-1, F, C), spec.shape[1], U)
-        parallel.allreduce_sum_(U)
+            add(spec.reshape(-1, F, C), spec.shape[1])
         self.metadata = [{"freqs_hash": _freqs_hash(freqs)}] * T
-        return finalize(U, T, lower_only=True)
+        return finish(T)
 
     def jackknife_hip(self, data, evaluate, fused=None):
         """Streaming jackknife on the device (connectivity_analysis.py:601-606,736-757; statistics/jackknifing.py):

@@ -1,6 +1,7 @@
 """`connectivityanalysis` metafunction: method = 'csd' | 'coh' | 'granger' | 'ppc' | 'corr', and beyond the reference
-'plv' | 'pli' | 'wpli' | 'wpli_debiased', which behave as 'ppc' does throughout, and 'dtf' | 'pdc', which take every rule
-of 'granger' (they are measures of the same Wilson factors).
+'plv' | 'pli' | 'wpli' | 'wpli_debiased', which behave as 'ppc' does throughout, 'dtf' | 'pdc', which take every rule
+of 'granger' (they are measures of the same Wilson factors), and the envelope correlations 'amplcorr' | 'powcorr' |
+'powcorr_ortho', which behave as 'ppc' does on the batched route and have no other.
 
 Two-stage pipeline of syncopy/connectivity/connectivity_analysis.py: single-trial
 cross-spectra accumulated over trials (ST stage, :587-599), then one evaluation on the
@@ -15,7 +16,7 @@ import numpy as np
 
 from ..datatype import (AnalogData, CrossSpectralData, SpectralData, require_real_analog, selected_channels,
                         selected_trialdefinition)
-from ..shared.const_def import connectivity_outputs, connectivityMethods, directedMethods, phaseMethods
+from ..shared.const_def import connectivity_outputs, connectivityMethods, directedMethods, envelopeMethods, phaseMethods
 from ..shared.errors import SPYTypeError, SPYValueError, SPYWarning
 from ..shared.kwarg_decorators import attached_selection, unwrap_cfg
 from ..shared.input_processors import process_foi, process_padding, process_taper
@@ -46,7 +47,13 @@ def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi
     the noise variances of the factorisation - the directed coherence instead of the directed transfer function, the
     generalised instead of the plain partial directed coherence.  Their `output` is 'abs' or 'pow' (the square, which
     sums to 1 over the senders of a receiver for dtf, over the receivers of a sender for pdc); the result is laid out
-    [sender, receiver] as for 'granger', the diagonal included."""
+    [sender, receiver] as for 'granger', the diagonal included.
+    The envelope correlations (not reference methods either; FieldTrip's `amplcorr`, `powcorr`, `powcorr_ortho`) are Pearson
+    correlations over the repetitions - every taper of every trial is one - of the amplitudes |x|, of the powers |x|^2, and
+    of the power of each channel with the power of the other orthogonalised to it (Hipp et al. 2012), averaged over the two
+    directions.  A channel without variance gives 0, not NaN; the diagonal is 1 (0 for such a channel), and 0 for
+    'powcorr_ortho'.  `output` is not used.  The sums per channel pair are float64: 1.07 GB at 256 channels x 2049 frequencies,
+    5.4 GB for 'powcorr_ortho'."""
     if precision not in ("float32", "reference", "auto"):
         raise SPYValueError("'float32', 'reference' or 'auto'", varname="precision", actual=str(precision))
     if not isinstance(data, (AnalogData, SpectralData)) or data.data is None:
@@ -200,7 +207,7 @@ def _connectivity_from_spectra(data, classes, method, keeptrials, output, comput
     if method in directedMethods and data.data.shape[data.dimord.index("time")] != len(data.sampleinfo):
         raise NotImplementedError(f"Time resolved {method} from tf-spectra not available")
     log_dict = {"method": method, "output": output, "keeptrials": keeptrials}
-    if cmb is not None and (method == "csd" or method in phaseMethods):
+    if cmb is not None and (method == "csd" or method in phaseMethods + envelopeMethods):
         # truly rectangular products (connectivity_analysis.py:503-529)
         st = classes["dyadic"](send_idx=cmb[0], send_N=len(cmb[0]), rec_idx=cmb[1], rec_N=len(cmb[1]))
     else:
@@ -262,9 +269,13 @@ def _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, p
     if nTrials == 1 and method != "corr":
         raise SPYValueError("multi-trial input data, spectral connectivity measures critically depend on trial "
                             "averaging!", "data", "only one trial")
-    if keeptrials is not False and method in ("coh", "granger") + phaseMethods + directedMethods:
+    if keeptrials is not False and method in ("coh", "granger") + phaseMethods + directedMethods + envelopeMethods:
         raise SPYValueError(f"False, trial averaging needed for method {method}!", varname="keeptrials",
                             actual=keeptrials)
+    if method in envelopeMethods and compute_method not in (None, "hip"):
+        raise NotImplementedError(f"method {method} runs on the batched route only (compute_method=None or 'hip'): the "
+                                  "per-trial engine keeps single-trial cross spectra, which are summed over the tapers "
+                                  "and cannot give a correlation over the repetitions")
     if method == "corr":
         return _cross_correlation(data, classes, keeptrials, foi, foilim, pad, polyremoval, compute_method)
     if isinstance(data, SpectralData):
@@ -323,9 +334,12 @@ def _ppc(data, classes, st, compute_method, log_dict, method="ppc"):
     """Pairwise phase consistency (connectivity_analysis.py:551-562,590,624-663): all trial pairs of the single-trial
     cross spectra.  With the kernels nothing is kept (K7 streams the trials); the per-trial engine path keeps the
     single-trial cross spectra as the reference does and hands them to classes["ppc"].  `method`: 'ppc' or one of its
-    siblings (phaseMethods), which take the same two paths with their own sums (K10) and classes[method]."""
+    siblings (phaseMethods), which take the same two paths with their own sums (K10) and classes[method], or an envelope
+    correlation (envelopeMethods), which takes the first path with its own sums (K12) and has no second."""
     from .. import backend
     out = CrossSpectralData(dimord=CrossSpectra.dimord)
+    if method in envelopeMethods and not hasattr(st, "ppc_hip"):
+        raise NotImplementedError(f"method {method} needs a single-trial routine with the batched route (ppc_hip)")
     if compute_method in (None, "hip") and hasattr(st, "ppc_hip"):
         st.initialize(data, out._stackingDim, chan_per_worker=None, keeptrials=False)
         # (F, Ci, Cj) from raw trials, (nTime, F, Ci, Cj) from spectra
@@ -368,11 +382,13 @@ def _run_stages(data, classes, st, method, keeptrials, output, compute_method, j
         # precision="auto": float64 transforms when the OUTPUT isolates a part of the complex coherency (its imaginary or real
         # part, its phase: 1.5e-7 of the modulus is not small against a part that nearly vanishes - as freqanalysis decides for
         # its own outputs), or when the DATA ask for them (CrossSpectra.needs_float64)
-        if (batched and hs.requested_precision() is None and method in ("coh", "granger") + phaseMethods + directedMethods
+        if (batched and hs.requested_precision() is None
+                and method in ("coh", "granger") + phaseMethods + directedMethods + envelopeMethods
                 and isinstance(data, AnalogData)
                 and ((method == "coh" and output in ("imag", "angle", "real"))
                      or (hasattr(st, "needs_float64")
-                         and st.needs_float64(data, "granger" if method in directedMethods else method)))):
+                         and st.needs_float64(data, "granger" if method in directedMethods
+                                              else "ppc" if method in envelopeMethods else method)))):
             stack.enter_context(hs.soft_reference())
         if method == "coh" and output in ("imag", "angle") and batched:
             from .. import backend
@@ -381,7 +397,7 @@ def _run_stages(data, classes, st, method, keeptrials, output, compute_method, j
 
 
 def _run_stages_impl(data, classes, st, method, keeptrials, output, compute_method, jackknife, log_dict):
-    if method in phaseMethods:
+    if method in phaseMethods + envelopeMethods:
         return _ppc(data, classes, st, compute_method, log_dict, method)
     if method == "coh":
         if output not in connectivity_outputs:
