@@ -350,6 +350,26 @@ int spyhip_envcorr_accumulate(spyhip_ctx* ctx, const void* spec_d, int ntrials, 
 int spyhip_envcorr_finalize(spyhip_ctx* ctx, const void* pair_d, const void* chan_d, int nfreq, int nchan, int64_t nrep,
                             int measure, void* out_d);
 
+/* ---- K13: phase slope index --------------------------------------------------
+ * Not in the reference (Nolte et al. 2008; FieldTrip's `psi`).  With c_ij(f) the complex64 coherency of
+ * spyhip_coh_normalize / spyhip_coh_from_accumulator (output 'fourier'; the diagonal's imaginary part zeroed) - but 0,
+ * not NaN, where the product of the two diagonal values is not positive - edge e joins the bins e and e + 1:
+ *   p_ij(e) = Im(conj(c_ij(e)) c_ij(e + 1)) = c.x(e) c.y(e + 1) - c.y(e) c.x(e + 1),  both products exact in float64;
+ *   half >= 1:  out[k, i, j] = sum_{e = k - half}^{k + half - 1} p_ij(e)  for half <= k <= nfreq - 1 - half, whole planes
+ *     NaN for the other k (the band does not fit); out float32 (nfreq, nchan, nchan);
+ *   half = 0:   out[0, i, j] = sum_{e = 0}^{nfreq - 2} p_ij(e); out float32 (1, nchan, nchan), nothing beyond is written.
+ *   Every sum over edges is float64 (a running window sum: newest edge added, oldest subtracted), rounded to float32
+ *   once.  Layout [f, sender, receiver]: out[f, i, j] > 0 where i leads j (S_ij = <x_i conj(x_j)>).  The result is
+ *   antisymmetric bit for bit (the upper triangle is the negated mirror of the lower), the diagonal exactly +0.
+ * spyhip_phaseslope: csd_d complex64 (nfreq, nchan, nchan), full Hermitian (its lower triangle is read).
+ * spyhip_phaseslope_from_accumulator: acc_d the raw lower-triangle accumulator of spyhip_csd_accumulate, not modified;
+ *   `scale` applied as spyhip_coh_from_accumulator applies it.  The same bits as spyhip_phaseslope on the finalised CSD.
+ *   half = 0 with more than one run of frequencies uses the context's scratch for float64 partial sums.
+ * -1: a null or non-positive argument, half < 0, nfreq < 2, 2 * half > nfreq - 1. */
+int spyhip_phaseslope(spyhip_ctx* ctx, const void* csd_d, int nfreq, int nchan, int half, void* out_d);
+int spyhip_phaseslope_from_accumulator(spyhip_ctx* ctx, const void* acc_d, int nfreq, int nchan, double scale, int half,
+                                       void* out_d);
+
 /* ---- K9: streaming jackknife of the coherence --------------------------------
  * Replaces, for method='coh' with jackknife=True, the T leave-one-out trial averages (statistics/jackknifing.py:14-108),
  * the AV stage on every replicate (connectivity_analysis.py:736-745) and the sums behind bias_var (:111-184):

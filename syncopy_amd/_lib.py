@@ -69,6 +69,8 @@ SIGNATURES = {
     "spyhip_plv_finalize": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, vp]),
     "spyhip_envcorr_accumulate": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "spyhip_envcorr_finalize": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int64, C.c_int, vp]),
+    "spyhip_phaseslope": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "spyhip_phaseslope_from_accumulator": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, vp]),
     "spyhip_jack_coh_accumulate": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int64,
                                              vp, vp]),
     "spyhip_ccov_nfft": (C.c_int, [C.c_int]),

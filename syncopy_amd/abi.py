@@ -213,6 +213,22 @@ class Device:
         acc.free()
         return res
 
+    # ---- K1 + K4 (+ C1) + K13
+    def phase_slope(self, queue, tapers, scale, nfft=None, detrend=0, half=0, ntrials_total=None):
+        """connectivityanalysis(method='psi'): (F, C, C) float32 [f, sender, receiver] for the half width `half` >= 1 in
+        bins, whole planes NaN where the band does not fit; half = 0: the whole axis, (1, C, C)."""
+        acc, K = self.csd_accumulator(queue, tapers, scale, nfft, detrend, False)
+        T = queue.ntrials if ntrials_total is None else int(ntrials_total)
+        F, Cn, _ = acc.shape
+        out = Buffer(self, (F if half else 1, Cn, Cn), np.float32)
+        try:
+            check(self.lib.spyhip_phaseslope_from_accumulator(self.handle, acc.ptr, F, Cn, 1.0 / (K * T), int(half), out.ptr),
+                  "spyhip_phaseslope_from_accumulator")
+            return out.numpy()
+        finally:
+            out.free()
+            acc.free()
+
     # ---- K1 + K7 / K10
     def phase_measure(self, queue, tapers, scale, nfft=None, detrend=0, method="wpli", ntrials_total=None):
         """connectivityanalysis(method='ppc' | 'plv' | 'pli' | 'wpli' | 'wpli_debiased'): (F, C, C) float32.  The sums

@@ -607,6 +607,35 @@ class csd_phase_exact:
         return False
 
 
+_trials_apart = [False]
+
+
+class csd_trials_apart:
+    """`with backend.csd_trials_apart(on):` - how the batched cross-spectral stage (CrossSpectra.compute_hip and pass 1 of
+    its jackknife) sums over trials inside the block: every trial's cross spectrum is accumulated on its own (a float32
+    chain over its tapers only, the very sum the per-trial engine forms) and the trials are added in float64, instead of
+    one float32 chain over the tapers of ALL trials.  That chain leaves some 1e-7 of the moduli in the imaginary parts,
+    which is the size of the parity criterion for a measure that is a small difference of unit-scale coherencies: the front
+    end enters this block for method 'psi'.  The price is what the jackknife's pass 2 pays as well: one update and one pass
+    over the (F, C, C) array per trial."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        _trials_apart.append(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        _trials_apart.pop()
+        return False
+
+
+def trials_apart():
+    """inside `with csd_trials_apart(True)`?"""
+    return _trials_apart[-1]
+
+
 def csd_accumulate(spec, acc, blocked=False, absmax=None, split=True, ranges=None):
     """acc[f,i,j] += sum_r spec[r,f,i] conj(spec[r,f,j]) on the lower triangle (MFMA).
     spec: (..., F, C) complex64 (leading dims flattened to rows), or with blocked=True the hand-over layout
@@ -933,6 +962,43 @@ def coh_from_accumulator(acc, scale, output="abs", out=None):
     ctx.bind_stream()
     check(ctx.lib.spyhip_coh_from_accumulator(ctx.handle, _ptr(acc), F, Cn, float(scale), kind, _ptr(out)),
           "spyhip_coh_from_accumulator")
+    return out
+
+
+def _phase_slope_out(src, half, out):
+    F, Cn, _ = src.shape
+    shape = (F if half else 1, Cn, Cn)
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=src.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
+    return out
+
+
+def phase_slope(csd, half, out=None):
+    """Phase slope index (K13) of the full Hermitian csd (F, C, C) complex64: float32 (F, C, C) [f, sender, receiver], the
+    sum over the 2 * half edges around each bin of Im(conj(c(f)) c(f + 1)) with c the coherency of coh_normalize; whole
+    planes NaN where the band does not fit.  half = 0: the sum over the whole axis, (1, C, C)."""
+    assert csd.is_cuda and csd.dtype == torch.complex64 and csd.is_contiguous() and csd.dim() == 3
+    F, Cn, _ = csd.shape
+    assert csd.shape[2] == Cn
+    out = _phase_slope_out(csd, half, out)
+    ctx = context(csd.device)
+    ctx.bind_stream()
+    check(ctx.lib.spyhip_phaseslope(ctx.handle, _ptr(csd), F, Cn, int(half), _ptr(out)), "spyhip_phaseslope")
+    return out
+
+
+def phase_slope_from_accumulator(acc, scale, half, out=None):
+    """phase_slope straight from the RAW lower-triangle accumulator of csd_accumulate (scale = 1/(tapers*trials)): the same
+    bits as csd_finalize + phase_slope.  acc is left untouched."""
+    assert acc.is_cuda and acc.dtype == torch.complex64 and acc.is_contiguous() and acc.dim() == 3
+    F, Cn, _ = acc.shape
+    assert acc.shape[2] == Cn
+    out = _phase_slope_out(acc, half, out)
+    ctx = context(acc.device)
+    ctx.bind_stream()
+    check(ctx.lib.spyhip_phaseslope_from_accumulator(ctx.handle, _ptr(acc), F, Cn, float(scale), int(half), _ptr(out)),
+          "spyhip_phaseslope_from_accumulator")
     return out
 
 

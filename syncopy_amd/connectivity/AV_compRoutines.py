@@ -123,6 +123,54 @@ class NormalizeCrossSpectra(_AverageRoutine):
         out.data = backend.to_host(res)
 
 
+def phaseslope_cF(csd_av_dat, half=0, chunkShape=None, noCompute=False):
+    """Phase slope index (Nolte et al. 2008, FieldTrip's `psi`; not in the reference) of the trial-averaged CSD
+    (nTime, nFreq, N, N): per time sample the sum over the 2 * half edges around each bin of Im(conj(c(f)) c(f + 1)), c the
+    coherency, as float32 (nTime, nFreq, N, N) [sender, receiver] with whole planes NaN where the band does not fit;
+    half = 0: the sum over the whole axis, (nTime, 1, N, N)."""
+    outShape = (csd_av_dat.shape[0], csd_av_dat.shape[1] if half else 1) + tuple(csd_av_dat.shape[2:])
+    if noCompute:
+        return outShape, spectralDTypes["abs"]
+    backend.require_gpu()
+    dev = torch.from_numpy(np.ascontiguousarray(csd_av_dat, dtype=np.complex64)).cuda()
+    res = [backend.phase_slope(dev[t], half) for t in range(dev.shape[0])]
+    return backend.to_host(torch.stack(res, dim=0))
+
+
+class PhaseSlope(_AverageRoutine):
+    """AV stage of method 'psi' (K13)."""
+    computeFunction = staticmethod(phaseslope_cF)
+    method = ""
+    valid_kws = ["half"]
+
+    def evaluate_device(self, csd):
+        """AV stage on one device CSD (F, C, C) -> (F or 1, C, C) float32; used by the streaming jackknife, one launch per
+        replicate."""
+        return backend.phase_slope(csd.contiguous(), self.cfg["half"])
+
+    def compute_hip(self, data, out):
+        raw = getattr(data, "_acc_raw", None)
+        if raw is not None:
+            # straight from the ST stage's raw accumulator.  One launch: a band couples neighbouring frequency ranges, so an
+            # accumulator that arrived range by range is waited for as a whole
+            stream = torch.cuda.current_stream(raw.device)
+            for _, _, ev in getattr(raw, "spyhip_range_events", None) or ():
+                stream.wait_event(ev)
+            res = backend.phase_slope_from_accumulator(raw, data._acc_scale, self.cfg["half"]).unsqueeze(0)
+            out._dev = res
+            out.set_pending(lambda: backend.to_host(res), tuple(res.shape), np.float32)
+            return
+        dev = self._device_input(data)
+        res = torch.stack([backend.phase_slope(dev[t].contiguous(), self.cfg["half"]) for t in range(dev.shape[0])], dim=0)
+        out._dev = res
+        out.set_pending(lambda: backend.to_host(res), tuple(res.shape), np.float32)
+
+    def process_metadata(self, data, out):
+        super().process_metadata(data, out)
+        if not self.cfg["half"]:
+            out.freq = np.array([np.mean(data.freq)])
+
+
 def granger_cF(csd_av_dat, rtol=5e-6, nIter=100, cond_max=1e4, chunkShape=None, noCompute=False):
     """Pairwise Granger-Geweke causality from the trial-averaged CSD (1, nFreq, N, N): regularisation,
     Wilson factorisation and the Granger formula all run on the device.  Returns (1, nFreq, N, N) float32

@@ -242,6 +242,21 @@ class CrossSpectra(ComputationalRoutine):
     valid_kws = ["samplerate", "nSamples", "foi", "taper", "taper_opt", "demean_taper", "polyremoval", "timeAxis",
                  "tapsmofrq", "nTaper", "pad", "output"]
 
+    def _sum_trials_apart(self, batches, F, C, device):
+        """backend.csd_trials_apart: every trial's cross spectrum on its own, the trials added in float64.  Returns (raw
+        lower-triangle accumulator (F, C, C) complex64 of the trials of `batches`, number of tapers)."""
+        acc64 = torch.zeros((F, C, C), dtype=torch.complex128, device=device)
+        one = torch.empty((F, C, C), dtype=torch.complex64, device=device)
+        K = 1
+        for _, spec in batches:
+            K = spec.spyhip_ntaper
+            am = getattr(spec, "spyhip_absmax", None)
+            for t in range(spec.shape[0]):
+                one.zero_()
+                backend.csd_accumulate(spec[t], one, absmax=am)
+                acc64 += one
+        return acc64.to(torch.complex64), K
+
     def compute_hip(self, data, out):
         """Trial-accumulated CSD straight from the in-HBM trial queue (MFMA rank-K updates).  A recording that is still
         being uploaded (first call on host data) is consumed chunk by chunk behind the copy (backend.Upload)."""
@@ -269,8 +284,13 @@ class CrossSpectra(ComputationalRoutine):
             ranges = backend.frequency_ranges(F, dev.device)
             if ranges:
                 backend.prewarm_landing(F * C * C * 4)       # (the float32 coherence outputs; complex ones find no block and allocate)
-        K = _csd_of_rows(dev, rows, chans, cfg["nSamples"], cfg["taper"], cfg["taper_opt"], cfg["demean_taper"], pr,
-                         freq_idx, getter, single_acc=not self.keeptrials, upload=upload, ranges=ranges) if rows else 1
+        if backend.trials_apart() and not self.keeptrials and rows:
+            acc, K = self._sum_trials_apart(
+                hs.run_mtmfft_batches(dev, rows, chans, cfg["nSamples"], cfg["taper"], cfg["taper_opt"], cfg["demean_taper"],
+                                      False, pr, freq_idx, "fourier", True, reuse=True, upload=upload), F, C, dev.device)
+        else:
+            K = _csd_of_rows(dev, rows, chans, cfg["nSamples"], cfg["taper"], cfg["taper_opt"], cfg["demean_taper"], pr,
+                             freq_idx, getter, single_acc=not self.keeptrials, upload=upload, ranges=ranges) if rows else 1
         data.device_data()                                  # (an upload in flight ends here at the latest)
         K = int(cfg["taper_opt"].get("Kmax", K)) if cfg["taper_opt"] else K
         self.metadata = [{"freqs_hash": _freqs_hash(freqs)}] * T
@@ -410,9 +430,12 @@ class CrossSpectra(ComputationalRoutine):
         # ---- pass 1: trial average
         S = torch.zeros((F, C, C), dtype=torch.complex64, device=dev.device)
         K = 1
-        for _, spec in batches(mine):
-            K = spec.spyhip_ntaper
-            backend.csd_accumulate(spec, S, absmax=getattr(spec, "spyhip_absmax", None))
+        if backend.trials_apart() and mine:
+            S, K = self._sum_trials_apart(batches(mine), F, C, dev.device)
+        else:
+            for _, spec in batches(mine):
+                K = spec.spyhip_ntaper
+                backend.csd_accumulate(spec, S, absmax=getattr(spec, "spyhip_absmax", None))
         K = int(cfg["taper_opt"].get("Kmax", K)) if cfg["taper_opt"] else K
         backend.csd_allreduce_(S)
         backend.csd_finalize(S, 1.0 / (K * T))

@@ -1,7 +1,8 @@
 """`connectivityanalysis` metafunction: method = 'csd' | 'coh' | 'granger' | 'ppc' | 'corr', and beyond the reference
 'plv' | 'pli' | 'wpli' | 'wpli_debiased', which behave as 'ppc' does throughout, 'dtf' | 'pdc', which take every rule
 of 'granger' (they are measures of the same Wilson factors), and the envelope correlations 'amplcorr' | 'powcorr' |
-'powcorr_ortho', which behave as 'ppc' does on the batched route and have no other.
+'powcorr_ortho', which behave as 'ppc' does on the batched route and have no other, and the phase slope index 'psi', which
+takes every rule of 'coh' and its own keyword `bandwidth`.
 
 Two-stage pipeline of syncopy/connectivity/connectivity_analysis.py: single-trial
 cross-spectra accumulated over trials (ST stage, :587-599), then one evaluation on the
@@ -21,7 +22,8 @@ from ..shared.errors import SPYTypeError, SPYValueError, SPYWarning
 from ..shared.kwarg_decorators import attached_selection, unwrap_cfg
 from ..shared.input_processors import process_foi, process_padding, process_taper
 from ..shared.tools import best_match
-from .AV_compRoutines import NormalizeCrossCov, NormalizeCrossSpectra, pairwise_phase_consistency, phase_lag
+from .AV_compRoutines import (NormalizeCrossCov, NormalizeCrossSpectra, PhaseSlope, pairwise_phase_consistency,
+                              phase_lag)
 from .ST_compRoutines import CrossCovariance, CrossSpectra, SpectralDyadicProduct
 
 
@@ -29,7 +31,7 @@ from .ST_compRoutines import CrossCovariance, CrossSpectra, SpectralDyadicProduc
 def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi=None, foilim=None, pad="maxperlen",
                          polyremoval=0, tapsmofrq=None, nTaper=None, taper="hann", taper_opt=None, jackknife=False,
                          channelcmb=None, select=None, compute_method=None, routine_classes=None, precision="auto",
-                         noise_weighted=False, **kwargs):
+                         noise_weighted=False, bandwidth=None, **kwargs):
     """Cross-spectral connectivity of AnalogData on MI355X (arguments as spy.connectivityanalysis,
     connectivity_analysis.py:51-67).
     `precision` (not a reference argument; as in `freqanalysis`): "reference" runs the taper product and the FFT of the
@@ -53,7 +55,16 @@ def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi
     of the power of each channel with the power of the other orthogonalised to it (Hipp et al. 2012), averaged over the two
     directions.  A channel without variance gives 0, not NaN; the diagonal is 1 (0 for such a channel), and 0 for
     'powcorr_ortho'.  `output` is not used.  The sums per channel pair are float64: 1.07 GB at 256 channels x 2049 frequencies,
-    5.4 GB for 'powcorr_ortho'."""
+    5.4 GB for 'powcorr_ortho'.
+    The phase slope index `method="psi"` (not a reference method either; Nolte et al. 2008, FieldTrip's `psi`) is the directed
+    measure that survives volume conduction: with c the complex coherency, the sum over the edges between neighbouring
+    frequencies of a band of Im(conj(c(f)) c(f + df)), laid out [sender, receiver] as for 'granger' - positive where the
+    sender leads the receiver, antisymmetric, diagonal 0.  `bandwidth` (Hz, this method only): the width of the band around
+    every frequency, h = max(1, round(bandwidth / (2 df))) bins to either side; the frequencies within h bins of either end
+    of the axis, where the band does not fit, are NaN.  `bandwidth=None`: the whole selected frequency range, one frequency
+    (the mean of the axis) in the result.  The frequency axis has to be equidistant.  Every rule of 'coh' holds
+    (`keeptrials=False`, more than one trial, `channelcmb` post-selects); `output` is not used.  `jackknife=True` adds
+    `jack_var` and `jack_bias` (NaN where psi is NaN): Nolte's normalised index is `psi / np.sqrt(jack_var)`."""
     if precision not in ("float32", "reference", "auto"):
         raise SPYValueError("'float32', 'reference' or 'auto'", varname="precision", actual=str(precision))
     if not isinstance(data, (AnalogData, SpectralData)) or data.data is None:
@@ -63,7 +74,7 @@ def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi
         raise SPYValueError("one of " + ", ".join(connectivityMethods), varname="method", actual=method)
     if not isinstance(jackknife, bool):
         raise SPYTypeError(jackknife, "jackknife", "boolean")
-    if jackknife and method not in ("coh", "granger"):
+    if jackknife and method not in ("coh", "granger", "psi"):
         SPYWarning(f"Jackknife is not available for method {method}")       # connectivity_analysis.py:310-317
         jackknife = False
     if not isinstance(noise_weighted, bool):
@@ -71,13 +82,21 @@ def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi
     if noise_weighted and method not in directedMethods:
         raise SPYValueError("False, noise weighting exists for the methods " + ", ".join(directedMethods) + " only",
                             varname="noise_weighted", actual=f"True with method {method}")
+    if bandwidth is not None:
+        if method != "psi":
+            raise SPYValueError("None, a bandwidth exists for the method psi only", varname="bandwidth",
+                                actual=f"{bandwidth} with method {method}")
+        if (isinstance(bandwidth, (bool, np.bool_)) or not isinstance(bandwidth, numbers.Real) or not np.isfinite(bandwidth)
+                or bandwidth <= 0):
+            raise SPYValueError("a positive number (Hz) or None", varname="bandwidth", actual=str(bandwidth))
     if method in directedMethods and output not in ("abs", "pow"):
         raise SPYValueError("'abs' or 'pow'", varname="output", actual=str(output))
     if polyremoval is not None:
         if not isinstance(polyremoval, numbers.Number) or polyremoval not in (0, 1):
             raise SPYValueError("0, 1 or None", varname="polyremoval", actual=polyremoval)
     classes = {"csd": CrossSpectra, "coh": NormalizeCrossSpectra, "dyadic": SpectralDyadicProduct,
-               "ppc": pairwise_phase_consistency, "ccov": CrossCovariance, "ccov_norm": NormalizeCrossCov}
+               "ppc": pairwise_phase_consistency, "ccov": CrossCovariance, "ccov_norm": NormalizeCrossCov,
+               "psi": PhaseSlope}
     classes.update({m: functools.partial(phase_lag, measure=m) for m in phaseMethods if m != "ppc"})
     try:
         from .AV_compRoutines import DirectedMeasure, GrangerCausality
@@ -95,9 +114,12 @@ def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi
 
         def run():
             return _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, polyremoval, tapsmofrq,
-                                 nTaper, taper, taper_opt, compute_method, jackknife, cmb)
+                                 nTaper, taper, taper_opt, compute_method, jackknife, cmb, bandwidth)
         with hs.precision(precision):
-            return run()
+            res = run()
+        if method == "psi":
+            res._cfg_derived = {"h": int(res.cfg["h"])}         # joins the call's record (unwrap_cfg)
+        return res
 
 
 def _parse_channelcmb(data, channelcmb):
@@ -196,7 +218,27 @@ def _pairwise_granger(data, classes, st, compute_method, log_dict, send, rec):
     return out
 
 
-def _connectivity_from_spectra(data, classes, method, keeptrials, output, compute_method, jackknife, cmb=None):
+def _psi_half(freq, bandwidth):
+    """method 'psi': the half width h in bins of a band of `bandwidth` Hz on the frequency axis `freq` (0: the whole axis)"""
+    freq = np.asarray(freq, dtype=np.float64)
+    if freq.size < 2:
+        raise SPYValueError("at least two frequencies, the phase slope is taken between neighbours", "foi/foilim",
+                            f"{freq.size} frequency")
+    df = np.diff(freq)
+    if not np.all(np.abs(df - df[0]) <= 1e-6 * abs(df[0])) or df[0] <= 0:
+        raise SPYValueError("an equidistant frequency axis, scattered frequencies make no slope", "foi",
+                            "frequencies that are not equidistant")
+    if bandwidth is None:
+        return 0
+    h = max(1, int(round(bandwidth / (2 * df[0]))))
+    if 2 * h > freq.size - 1:
+        raise SPYValueError(f"a bandwidth of at most {(freq.size - 1) * df[0]:g} Hz on these {freq.size} frequencies",
+                            varname="bandwidth", actual=f"{bandwidth} Hz: a band of 2 x {h} bins does not fit")
+    return h
+
+
+def _connectivity_from_spectra(data, classes, method, keeptrials, output, compute_method, jackknife, cmb=None,
+                               bandwidth=None):
     """SpectralData input (connectivity_analysis.py:475-538): the spectra exist already, the ST stage is the dyadic
     product; everything about tapers / padding / frequencies was decided in freqanalysis."""
     if not np.issubdtype(np.asarray(data.data).dtype, np.complexfloating):
@@ -207,6 +249,8 @@ def _connectivity_from_spectra(data, classes, method, keeptrials, output, comput
     if method in directedMethods and data.data.shape[data.dimord.index("time")] != len(data.sampleinfo):
         raise NotImplementedError(f"Time resolved {method} from tf-spectra not available")
     log_dict = {"method": method, "output": output, "keeptrials": keeptrials}
+    if method == "psi":
+        log_dict.update(bandwidth=bandwidth, h=_psi_half(data.freq, bandwidth))
     if cmb is not None and (method == "csd" or method in phaseMethods + envelopeMethods):
         # truly rectangular products (connectivity_analysis.py:503-529)
         st = classes["dyadic"](send_idx=cmb[0], send_N=len(cmb[0]), rec_idx=cmb[1], rec_N=len(cmb[1]))
@@ -224,7 +268,7 @@ def _connectivity_from_spectra(data, classes, method, keeptrials, output, comput
         info = dict(out.info)
         out = _post_select(out, *cmb)
         out.info.update(info)
-    if cmb is not None and method == "coh":
+    if cmb is not None and method in ("coh", "psi"):
         jack = {k: getattr(out, k, None) for k in ("jack_var", "jack_bias")}
         out = _post_select(out, *cmb)
         for k, v in jack.items():
@@ -260,7 +304,7 @@ def _cross_correlation(data, classes, keeptrials, foi, foilim, pad, polyremoval,
 
 
 def _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, polyremoval, tapsmofrq, nTaper, taper,
-                  taper_opt, compute_method, jackknife=False, cmb=None):
+                  taper_opt, compute_method, jackknife=False, cmb=None, bandwidth=None):
     fs = data.samplerate
     timeAxis = data.dimord.index("time")
     trl = selected_trialdefinition(data)
@@ -269,7 +313,7 @@ def _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, p
     if nTrials == 1 and method != "corr":
         raise SPYValueError("multi-trial input data, spectral connectivity measures critically depend on trial "
                             "averaging!", "data", "only one trial")
-    if keeptrials is not False and method in ("coh", "granger") + phaseMethods + directedMethods + envelopeMethods:
+    if keeptrials is not False and method in ("coh", "granger", "psi") + phaseMethods + directedMethods + envelopeMethods:
         raise SPYValueError(f"False, trial averaging needed for method {method}!", varname="keeptrials",
                             actual=keeptrials)
     if method in envelopeMethods and compute_method not in (None, "hip"):
@@ -279,7 +323,8 @@ def _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, p
     if method == "corr":
         return _cross_correlation(data, classes, keeptrials, foi, foilim, pad, polyremoval, compute_method)
     if isinstance(data, SpectralData):
-        return _connectivity_from_spectra(data, classes, method, keeptrials, output, compute_method, jackknife, cmb)
+        return _connectivity_from_spectra(data, classes, method, keeptrials, output, compute_method, jackknife, cmb,
+                                          bandwidth)
     nSamples = process_padding(pad, lenTrials, fs)
     foi, foilim = process_foi(foi, foilim, fs)
     if method == "granger" or method in directedMethods:
@@ -302,6 +347,8 @@ def _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, p
                                      samplerate=fs, nSamples=lenTrials.mean(), output="pow")
     log_dict = {"method": method, "output": output, "keeptrials": keeptrials, "polyremoval": polyremoval,
                 "pad": pad, "foi": foi, "taper": taper, "taper_opt": taper_opt}
+    if method == "psi":
+        log_dict.update(bandwidth=bandwidth, h=_psi_half(foi, bandwidth))
 
     st = classes["csd"](samplerate=fs, nSamples=nSamples, taper=taper, taper_opt=taper_opt,
                         demean_taper=(method == "granger" or method in directedMethods), polyremoval=polyremoval, timeAxis=timeAxis, foi=foi)
@@ -383,15 +430,20 @@ def _run_stages(data, classes, st, method, keeptrials, output, compute_method, j
         # part, its phase: 1.5e-7 of the modulus is not small against a part that nearly vanishes - as freqanalysis decides for
         # its own outputs), or when the DATA ask for them (CrossSpectra.needs_float64)
         if (batched and hs.requested_precision() is None
-                and method in ("coh", "granger") + phaseMethods + directedMethods + envelopeMethods
+                and method in ("coh", "granger", "psi") + phaseMethods + directedMethods + envelopeMethods
                 and isinstance(data, AnalogData)
                 and ((method == "coh" and output in ("imag", "angle", "real"))
+                     or method == "psi"        # sums of imaginary parts of coherency products: as coh with output="imag"
                      or (hasattr(st, "needs_float64")
                          and st.needs_float64(data, "granger" if method in directedMethods
                                               else "ppc" if method in envelopeMethods else method)))):
             stack.enter_context(hs.soft_reference())
-        if method == "coh" and output in ("imag", "angle") and batched:
-            from .. import backend
+        from .. import backend
+        if method == "psi" and batched:
+            # a small difference of unit-scale coherencies: every trial's cross spectrum on its own, the trials added in float64
+            stack.enter_context(backend.csd_trials_apart(True))
+        # (psi on either route: its AV stage is the device's whatever engine accumulates the cross spectra)
+        if method == "psi" or (method == "coh" and output in ("imag", "angle") and batched):
             stack.enter_context(backend.csd_phase_exact(True))
         return _run_stages_impl(data, classes, st, method, keeptrials, output, compute_method, jackknife, log_dict)
 
@@ -403,6 +455,8 @@ def _run_stages_impl(data, classes, st, method, keeptrials, output, compute_meth
         if output not in connectivity_outputs:
             raise SPYValueError(f"one of {sorted(connectivity_outputs)}", varname="output", actual=output)
         av = classes["coh"](output=output)
+    elif method == "psi":
+        av = classes["psi"](half=log_dict["h"])
     elif method == "granger":
         if "granger" not in classes:
             raise NotImplementedError("Wilson/Granger kernels are not part of this build")

@@ -11,7 +11,7 @@ availableTapers = [w for w in windows.__all__ if w not in ("get_window", "expone
 availablePaddingOpt = ["maxperlen", "nextpow2"]
 availableMethods = ("mtmfft", "mtmconvol", "wavelet", "superlet", "welch")
 connectivityMethods = ("coh", "corr", "csd", "granger", "ppc", "plv", "pli", "wpli", "wpli_debiased", "dtf", "pdc",
-                       "amplcorr", "powcorr", "powcorr_ortho")
+                       "amplcorr", "powcorr", "powcorr_ortho", "psi")
 # ppc and its siblings beyond the reference: non-linear in the single-trial cross spectrum, accumulated over trials
 phaseMethods = ("ppc", "plv", "pli", "wpli", "wpli_debiased")
 # beyond the reference as well: directed measures of the Wilson factors, which take every rule of granger

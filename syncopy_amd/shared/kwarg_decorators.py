@@ -117,6 +117,8 @@ def unwrap_cfg(func):
         record = StructDict({k: v for k, v in (getattr(data, "cfg", None) or {}).items() if isinstance(v, dict)})
         record[func.__name__] = StructDict({k: v for k, v in cfg.items()
                                             if k not in ("compute_method", "routine_classes")})
+        # what the call derived from its parameters and wants on record (the half width `h` of method 'psi')
+        record[func.__name__].update(getattr(res, "_cfg_derived", None) or {})
         try:
             res.cfg = record
         except AttributeError:
