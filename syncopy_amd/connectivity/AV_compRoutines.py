@@ -21,26 +21,10 @@ def normalize_csd_cF(csd_av_dat, output="abs", chunkShape=None, noCompute=False)
     return backend.to_host(torch.stack(res, dim=0))
 
 
-def pairwise_phase_consistency(st_csd):
-    """PPC of kept single-trial cross spectra (T, F, Ni, Nj) complex64 -> (1, F, Ni, Nj) float32: what the loop over
-    PPC_column routines and its weighted average amount to (connectivity_analysis.py:624-663;
-    ST_compRoutines.py:159-233), through K7's closed form - unit phasors summed over trials, then
-    (|U|^2 - T)/(T(T-1))."""
-    backend.require_gpu()
-    st_csd = np.asarray(st_csd)
-    T = st_csd.shape[0]
-    acc = torch.zeros(st_csd.shape[1:], dtype=torch.complex64, device="cuda")
-    per = max(1, int((1 << 30) // max(1, acc.numel() * 8)))
-    for t0 in range(0, T, per):
-        dev = torch.from_numpy(np.ascontiguousarray(st_csd[t0:t0 + per], dtype=np.complex64)).cuda()
-        backend.ppc_accumulate_csd(dev, acc)
-    return backend.to_host(backend.ppc_finalize(acc, T, lower_only=False))[np.newaxis]
-
-
 def phase_lag(st_csd, measure):
-    """'plv' | 'pli' | 'wpli' | 'wpli_debiased' of kept single-trial cross spectra (T, F, Ni, Nj) complex64 ->
-    (1, F, Ni, Nj) float32 (not in the reference): the sums over trials of the batched path (backend.phase_accumulator),
-    taken element by element, then its finalizer on the rectangle."""
+    """'ppc' | 'plv' | 'pli' | 'wpli' | 'wpli_debiased' of kept single-trial cross spectra (T, F, Ni, Nj) complex64 ->
+    (1, F, Ni, Nj) float32 (all but the first not in the reference): the sums over trials of the batched path
+    (backend.phase_accumulator), taken element by element, then its finalizer on the rectangle."""
     backend.require_gpu()
     st_csd = np.asarray(st_csd)
     T = st_csd.shape[0]
@@ -50,6 +34,14 @@ def phase_lag(st_csd, measure):
         dev = torch.from_numpy(np.ascontiguousarray(st_csd[t0:t0 + per], dtype=np.complex64)).cuda()
         accumulate_csd(dev, acc)
     return backend.to_host(finalize(acc, T, lower_only=False))[np.newaxis]
+
+
+def pairwise_phase_consistency(st_csd):
+    """PPC of kept single-trial cross spectra (T, F, Ni, Nj) complex64 -> (1, F, Ni, Nj) float32: what the loop over
+    PPC_column routines and its weighted average amount to (connectivity_analysis.py:624-663;
+    ST_compRoutines.py:159-233), through K7's closed form - unit phasors summed over trials, then
+    (|U|^2 - T)/(T(T-1))."""
+    return phase_lag(st_csd, "ppc")
 
 
 class _AverageRoutine(ComputationalRoutine):
@@ -68,6 +60,14 @@ class _AverageRoutine(ComputationalRoutine):
         if dev is None:
             dev = torch.from_numpy(np.ascontiguousarray(data.data, dtype=np.complex64)).cuda()
         return dev
+
+    @staticmethod
+    def _keep_on_device(out, res, fetch=None):
+        """`res` is the result and stays in HBM until somebody reads `.data` (then one pinned, chunked copy, or `fetch`): a
+        chained analysis or a plot of a few channel pairs never pays for the whole array (0.5 GB of coherence)."""
+        out._dev = res
+        out.set_pending(fetch or (lambda: backend.to_host(res)), tuple(res.shape),
+                        np.complex64 if res.is_complex() else np.float32)
 
     def process_metadata(self, data, out):
         out.channel_i = np.array(data.channel_i)
@@ -102,19 +102,12 @@ class NormalizeCrossSpectra(_AverageRoutine):
             # can read, computational_routine.py:1022-1036)
             res, landing = backend.coh_pipeline(raw, data._acc_scale, self.cfg["output"], events)
             res = res.unsqueeze(0)
-            out._dev = res
             shape = tuple(res.shape)
-            out.set_pending((lambda: landing.array().reshape(shape)) if landing is not None else (lambda: backend.to_host(res)),
-                            shape, np.complex64 if res.is_complex() else np.float32)
+            self._keep_on_device(out, res, (lambda: landing.array().reshape(shape)) if landing is not None else None)
             return
         if raw is not None:
             # straight from the ST stage's raw accumulator: scale + normalise + convert + mirror in one pass
-            res = backend.coh_from_accumulator(raw, data._acc_scale, self.cfg["output"]).unsqueeze(0)
-            out._dev = res
-            # the 0.5 GB result stays in HBM until somebody reads `.data` (then one pinned, chunked copy): a chained
-            # analysis or a plot of a few channel pairs never pays for the whole array
-            out.set_pending(lambda: backend.to_host(res), tuple(res.shape),
-                            np.complex64 if res.is_complex() else np.float32)
+            self._keep_on_device(out, backend.coh_from_accumulator(raw, data._acc_scale, self.cfg["output"]).unsqueeze(0))
             return
         dev = self._device_input(data)
         res = torch.stack([backend.coh_normalize(dev[t].contiguous(), self.cfg["output"])
@@ -156,14 +149,11 @@ class PhaseSlope(_AverageRoutine):
             stream = torch.cuda.current_stream(raw.device)
             for _, _, ev in getattr(raw, "spyhip_range_events", None) or ():
                 stream.wait_event(ev)
-            res = backend.phase_slope_from_accumulator(raw, data._acc_scale, self.cfg["half"]).unsqueeze(0)
-            out._dev = res
-            out.set_pending(lambda: backend.to_host(res), tuple(res.shape), np.float32)
+            self._keep_on_device(out, backend.phase_slope_from_accumulator(raw, data._acc_scale, self.cfg["half"]).unsqueeze(0))
             return
         dev = self._device_input(data)
-        res = torch.stack([backend.phase_slope(dev[t].contiguous(), self.cfg["half"]) for t in range(dev.shape[0])], dim=0)
-        out._dev = res
-        out.set_pending(lambda: backend.to_host(res), tuple(res.shape), np.float32)
+        self._keep_on_device(out, torch.stack([backend.phase_slope(dev[t].contiguous(), self.cfg["half"])
+                                               for t in range(dev.shape[0])], dim=0))
 
     def process_metadata(self, data, out):
         super().process_metadata(data, out)
@@ -193,11 +183,32 @@ def _granger_metadata(meta):
     }
 
 
-class GrangerCausality(_AverageRoutine):
-    computeFunction = staticmethod(granger_cF)
+class _WilsonRoutine(_AverageRoutine):
+    """AV stages on the Wilson factorisation of a trial-averaged CSD.  A subclass supplies `_of_plane(csd)`: one device
+    CSD (F, C, C) every rank holds -> (its measure (F, C, C) float32, the factorisation's metadata)."""
     method = ""
-    valid_kws = ["rtol", "nIter", "cond_max"]
     metadata_keys = ("converged", "max rel. err", "reg. factor", "initial cond. num")
+
+    def compute_hip(self, data, out):
+        dev = self._device_input(data)
+        res, self.metadata = [], []
+        for t in range(dev.shape[0]):            # one trial average, or the jackknife's leave-one-out replicates
+            plane, meta = self._of_plane(dev[t].contiguous())
+            res.append(plane)
+            self.metadata.append(_granger_metadata(meta))
+        out._dev = torch.stack(res, dim=0)
+        out.data = backend.to_host(out._dev)
+
+    def process_metadata(self, data, out):
+        super().process_metadata(data, out)
+        for key, value in (self.metadata[0] or {}).items():
+            label, cast = key.split("--")
+            out.info[label] = bool(value) if cast == "bool" else float(value)
+
+
+class GrangerCausality(_WilsonRoutine):
+    computeFunction = staticmethod(granger_cF)
+    valid_kws = ["rtol", "nIter", "cond_max"]
 
     def evaluate_device(self, csd):
         """AV stage on one device CSD (F, C, C) -> Granger (F, C, C) float32; keeps the metadata of the first call
@@ -219,21 +230,7 @@ class GrangerCausality(_AverageRoutine):
             return granger_hip_sharded(csd, **kw)
         return backend.granger(csd, **kw)
 
-    def compute_hip(self, data, out):
-        dev = self._device_input(data)
-        res, self.metadata = [], []
-        for t in range(dev.shape[0]):            # one trial average, or the jackknife's leave-one-out replicates
-            G, meta = self._granger(dev[t].contiguous())
-            res.append(G)
-            self.metadata.append(_granger_metadata(meta))
-        out._dev = torch.stack(res, dim=0)
-        out.data = backend.to_host(out._dev)
-
-    def process_metadata(self, data, out):
-        super().process_metadata(data, out)
-        for key, value in (self.metadata[0] or {}).items():
-            label, cast = key.split("--")
-            out.info[label] = bool(value) if cast == "bool" else float(value)
+    _of_plane = _granger
 
 
 def directed_cF(csd_av_dat, method="dtf", noise_weighted=False, output="abs", rtol=5e-6, nIter=100, cond_max=1e4,
@@ -253,34 +250,16 @@ def directed_cF(csd_av_dat, method="dtf", noise_weighted=False, output="abs", rt
     return backend.to_host(res)[None, ...], _granger_metadata(meta)
 
 
-class DirectedMeasure(_AverageRoutine):
+class DirectedMeasure(_WilsonRoutine):
     """AV stage of method 'dtf' / 'pdc'.  Every rank of a process group factorises the whole CSD it holds: the
-    frequency shards of GrangerCausality are not used here."""
+    frequency shards of GrangerCausality are not used here.  (No `evaluate_device`: there is no jackknife of these.)"""
     computeFunction = staticmethod(directed_cF)
-    method = ""
     valid_kws = ["method", "noise_weighted", "output", "rtol", "nIter", "cond_max"]
-    metadata_keys = GrangerCausality.metadata_keys
 
-    def process_metadata(self, data, out):
-        super().process_metadata(data, out)
-        for key, value in (self.metadata[0] or {}).items():
-            label, cast = key.split("--")
-            out.info[label] = bool(value) if cast == "bool" else float(value)
-
-    def _directed(self, csd):
+    def _of_plane(self, csd):
         cfg = self.cfg
         return backend.directed(csd, cfg["method"], noise_weighted=cfg["noise_weighted"], squared=(cfg["output"] == "pow"),
                                 rtol=cfg["rtol"], niter=cfg["nIter"], cond_max=cfg["cond_max"], eps_max=1e-1)
-
-    def compute_hip(self, data, out):
-        dev = self._device_input(data)
-        res, self.metadata = [], []
-        for t in range(dev.shape[0]):
-            D, meta = self._directed(dev[t].contiguous())
-            res.append(D)
-            self.metadata.append(_granger_metadata(meta))
-        out._dev = torch.stack(res, dim=0)
-        out.data = backend.to_host(out._dev)
 
 
 def normalize_ccov_cF(trl_av_dat, chunkShape=None, noCompute=False):

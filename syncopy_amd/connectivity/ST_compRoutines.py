@@ -29,15 +29,35 @@ def _freq_selection(nSamples, samplerate, foi):
     return freqs, freq_idx
 
 
-def _csd_of_rows(dev, rows, chans, nSamples, taper, taper_opt, demean_taper, polyremoval, freq_idx, acc_of_trial,
-                 single_acc=False, upload=None, ranges=None):
-    """Accumulate sum_k X_k X_k^H of every trial in `rows` into `acc_of_trial(i)` (device (F,C,C) c64).
+def _polyremoval(polyremoval):
+    """The detrending order as the transform plans take it: 0 or 1, None for none (None, False and anything else)."""
+    return polyremoval if polyremoval in (0, 1) and polyremoval is not False else None
+
+
+class _TrialStream:
+    """The tapered spectra of trials that lie in one device tensor, batch by batch: the one place of this module that asks
+    for transforms.  `cfg`: nSamples, taper, taper_opt, demean_taper and polyremoval of the routine; `upload`: the copy of
+    `dev` that is still in flight (backend.Upload), if any.  CrossSpectra._stream adds what it resolves of a data object."""
+
+    def __init__(self, dev, chans, cfg, freq_idx, upload=None):
+        self.dev, self.chans, self.cfg, self.freq_idx, self.upload = dev, chans, cfg, freq_idx, upload
+        self.polyremoval = _polyremoval(cfg["polyremoval"])
+
+    def batches(self, rows, output="fourier", whole_axis=False, blocked=False):
+        """(trial indices within `rows`, spectra) of hs.run_mtmfft_batches: every taper of the selected frequencies
+        (`whole_axis`: of all of them), one shared hand-over buffer."""
+        cfg = self.cfg
+        return hs.run_mtmfft_batches(self.dev, rows, self.chans, cfg["nSamples"], cfg["taper"], cfg["taper_opt"],
+                                     cfg["demean_taper"], False, self.polyremoval, None if whole_axis else self.freq_idx,
+                                     output, True, blocked=blocked, reuse=True, upload=self.upload)
+
+
+def _csd_of_rows(stream, rows, acc_of_trial, single_acc=False, ranges=None):
+    """Accumulate sum_k X_k X_k^H of every trial in `rows` of `stream` into `acc_of_trial(i)` (device (F,C,C) c64).
     `single_acc`: every trial lands in the same accumulator, so the spectra may take the channel-blocked
     hand-over layout between the FFT and the CSD kernel (coalesced stores, identical results)."""
     ntaper = 1
-    for sel, spec in hs.run_mtmfft_batches(dev, rows, chans, nSamples, taper, taper_opt, demean_taper, False,
-                                           polyremoval, freq_idx, "fourier", True,
-                                           blocked=single_acc and backend.USE_BLOCKED_HANDOVER, reuse=True, upload=upload):
+    for sel, spec in stream.batches(rows, blocked=single_acc and backend.USE_BLOCKED_HANDOVER):
         ntaper = spec.spyhip_ntaper
         if spec.spyhip_blocked:
             backend.csd_accumulate(spec, acc_of_trial(sel[0]), blocked=True)
@@ -72,10 +92,10 @@ def cross_spectra_cF(trl_dat, samplerate=1, nSamples=None, foi=None, taper="hann
     backend.require_gpu()
     dev = torch.from_numpy(np.ascontiguousarray(dat, dtype=np.float32)).cuda()
     acc = torch.zeros(outShape[1:], dtype=torch.complex64, device=dev.device)
-    pr = polyremoval if polyremoval in (0, 1) and polyremoval is not False else None
+    stream = _TrialStream(dev, None, dict(nSamples=nSamples, taper=taper, taper_opt=taper_opt, demean_taper=demean_taper,
+                                          polyremoval=polyremoval), freq_idx)
     with hs.per_trial_route():
-        K = _csd_of_rows(dev, [(0, dev.shape[0])], None, nSamples, taper, taper_opt, demean_taper, pr, freq_idx,
-                         lambda i: acc, single_acc=True)
+        K = _csd_of_rows(stream, [(0, dev.shape[0])], lambda i: acc, single_acc=True)
     backend.csd_finalize(acc, 1.0 / K)
     return backend.to_host(acc)[np.newaxis], {"freqs_hash": _freqs_hash(freqs)}
 
@@ -159,21 +179,25 @@ class SpectralDyadicProduct(ComputationalRoutine):
     computeFunction = staticmethod(spectral_dyadic_product_cF)
     valid_kws = ["send_idx", "send_N", "rec_idx", "rec_N", "output"]
 
-    def compute_hip(self, data, out):
-        """All trials in one go: the whole (rows, nFreq, N) block of a rank's trials goes through the MFMA kernel
-        (keeptrials=False), or one launch per time sample (keeptrials=True)."""
+    def _selected_spectra(self, data):
+        """What both entry points start from: (rows of every trial, their set of lengths, the host spectra (rows, K, F, C) of
+        the channels that take part, `sub`) - `sub` (_cmb_union) where `channelcmb` asks for a rectangle, else None."""
         rows, chans = trial_rows(data), selected_channels(data)
-        T = self.numTrials
-        mine = self.my_trials()
         host = np.asarray(data.data)
         sub = _cmb_union(self.cfg.get("send_idx"), self.cfg.get("rec_idx"))
         if sub is not None:
             chans = list(sub[0])                       # a channel selection next to channelcmb is ruled out upstream
         if chans is not None:
             host = host[..., chans]
-        F, C = self.targetShapes[0][1], host.shape[-1]
-        K = host.shape[1]
-        lens = {rows[k][1] - rows[k][0] for k in range(T)}
+        return rows, {rows[k][1] - rows[k][0] for k in range(self.numTrials)}, host, sub
+
+    def compute_hip(self, data, out):
+        """All trials in one go: the whole (rows, nFreq, N) block of a rank's trials goes through the MFMA kernel
+        (keeptrials=False), or one launch per time sample (keeptrials=True)."""
+        rows, lens, host, sub = self._selected_spectra(data)
+        T = self.numTrials
+        mine = self.my_trials()
+        K, F, C = host.shape[1:]
         if self.keeptrials or lens != {1}:
             # time-resolved spectra or kept trials: per-trial compute function (one launch per time sample)
             kw = {} if sub is None else dict(send_idx=sub[1], rec_idx=sub[2])
@@ -200,19 +224,12 @@ class SpectralDyadicProduct(ComputationalRoutine):
         cut out of the channels that occur at all.  `measure`: 'ppc', or one of its siblings 'plv' (K7's sums, another
         finalizer), 'pli', 'wpli', 'wpli_debiased' (K10: backend.phase_accumulator), or an envelope correlation 'amplcorr',
         'powcorr', 'powcorr_ortho' (K12: backend.envelope_accumulator).  Returns (nTime, F, C_i, C_j) on the device."""
-        rows, chans = trial_rows(data), selected_channels(data)
+        rows, lens, host, sub = self._selected_spectra(data)
         T = self.numTrials
-        lens = {rows[k][1] - rows[k][0] for k in range(T)}
         if len(lens) != 1:
             raise SPYValueError("trials of equal length", varname="data",
                                 actual=f"time-resolved spectra with {sorted(lens)} samples per trial")
         L = lens.pop()
-        host = np.asarray(data.data)
-        sub = _cmb_union(self.cfg.get("send_idx"), self.cfg.get("rec_idx"))
-        if sub is not None:
-            chans = list(sub[0])
-        if chans is not None:
-            host = host[..., chans]
         K, F, C = host.shape[1:]
         mine = self.my_trials()
         first = np.array([rows[k][0] for k in mine], dtype=np.int64)
@@ -242,6 +259,25 @@ class CrossSpectra(ComputationalRoutine):
     valid_kws = ["samplerate", "nSamples", "foi", "taper", "taper_opt", "demean_taper", "polyremoval", "timeAxis",
                  "tapsmofrq", "nTaper", "pad", "output"]
 
+    def _stream(self, data, partial=False):
+        """The stream of `data`'s trials for this routine (_TrialStream), with what every entry point resolves first: `rows`
+        of all trials in the device tensor's coordinates and, once the routine is initialised (needs_float64 is asked
+        before that), `F`, `C`, the number of trials `T`, `mine` - the rows of this rank's contiguous trial shard - and the
+        `metadata` of the T trials.  `partial`: an upload that is still in flight is consumed behind the copy."""
+        cfg = self.cfg
+        dev = data.device_data(partial=True) if partial else data.device_data()
+        upload = data.upload_in_flight() if partial else None
+        rows = device_rows(data)
+        nS = cfg["nSamples"] if cfg["nSamples"] is not None else rows[0][1] - rows[0][0]
+        freqs, freq_idx = _freq_selection(nS, cfg["samplerate"], cfg["foi"])
+        stream = _TrialStream(dev, selected_channels(data), cfg, freq_idx, upload)
+        stream.rows = rows
+        if self.numTrials is not None:
+            stream.F, stream.C, stream.T = self.targetShapes[0][1], self.targetShapes[0][2], self.numTrials
+            stream.mine = [rows[k] for k in self.my_trials()]
+            stream.metadata = [{"freqs_hash": _freqs_hash(freqs)}] * stream.T
+        return stream
+
     def _sum_trials_apart(self, batches, F, C, device):
         """backend.csd_trials_apart: every trial's cross spectrum on its own, the trials added in float64.  Returns (raw
         lower-triangle accumulator (F, C, C) complex64 of the trials of `batches`, number of tapers)."""
@@ -261,16 +297,8 @@ class CrossSpectra(ComputationalRoutine):
         """Trial-accumulated CSD straight from the in-HBM trial queue (MFMA rank-K updates).  A recording that is still
         being uploaded (first call on host data) is consumed chunk by chunk behind the copy (backend.Upload)."""
         cfg = self.cfg
-        dev = data.device_data(partial=True)
-        upload = data.upload_in_flight()
-        rows, chans = device_rows(data), selected_channels(data)
-        nS = cfg["nSamples"] if cfg["nSamples"] is not None else rows[0][1] - rows[0][0]
-        freqs, freq_idx = _freq_selection(nS, cfg["samplerate"], cfg["foi"])
-        pr = cfg["polyremoval"] if cfg["polyremoval"] in (0, 1) and cfg["polyremoval"] is not False else None
-        F, C = self.targetShapes[0][1], self.targetShapes[0][2]
-        T = self.numTrials
-        mine = self.my_trials()                            # this rank's contiguous trial shard
-        rows = [rows[k] for k in mine]
+        stream = self._stream(data, partial=True)
+        dev, rows, F, C, T = stream.dev, stream.mine, stream.F, stream.C, stream.T
         if self.keeptrials:
             acc = torch.zeros((len(rows), F, C, C), dtype=torch.complex64, device=dev.device)
             getter = lambda i: acc[i]                      # noqa: E731
@@ -285,15 +313,12 @@ class CrossSpectra(ComputationalRoutine):
             if ranges:
                 backend.prewarm_landing(F * C * C * 4)       # (the float32 coherence outputs; complex ones find no block and allocate)
         if backend.trials_apart() and not self.keeptrials and rows:
-            acc, K = self._sum_trials_apart(
-                hs.run_mtmfft_batches(dev, rows, chans, cfg["nSamples"], cfg["taper"], cfg["taper_opt"], cfg["demean_taper"],
-                                      False, pr, freq_idx, "fourier", True, reuse=True, upload=upload), F, C, dev.device)
+            acc, K = self._sum_trials_apart(stream.batches(rows), F, C, dev.device)
         else:
-            K = _csd_of_rows(dev, rows, chans, cfg["nSamples"], cfg["taper"], cfg["taper_opt"], cfg["demean_taper"], pr,
-                             freq_idx, getter, single_acc=not self.keeptrials, upload=upload, ranges=ranges) if rows else 1
+            K = _csd_of_rows(stream, rows, getter, single_acc=not self.keeptrials, ranges=ranges) if rows else 1
         data.device_data()                                  # (an upload in flight ends here at the latest)
         K = int(cfg["taper_opt"].get("Kmax", K)) if cfg["taper_opt"] else K
-        self.metadata = [{"freqs_hash": _freqs_hash(freqs)}] * T
+        self.metadata = stream.metadata
         if self.keeptrials:
             for t in range(len(rows)):
                 backend.csd_finalize(acc[t], 1.0 / K)
@@ -335,11 +360,8 @@ class CrossSpectra(ComputationalRoutine):
         set of options: the measured ratio is kept on the data object until its array changes (`invalidate`); AR(2)-type
         data never asks, line noise 50 dB above the floor or 1/f spectra over four decades do."""
         cfg = self.cfg
-        dev = data.device_data(partial=True)
-        upload = data.upload_in_flight()
-        rows, chans = device_rows(data), selected_channels(data)
-        nS = cfg["nSamples"] if cfg["nSamples"] is not None else rows[0][1] - rows[0][0]
-        _, freq_idx = _freq_selection(nS, cfg["samplerate"], cfg["foi"])
+        stream = self._stream(data, partial=True)
+        rows, chans, freq_idx = stream.rows, stream.chans, stream.freq_idx
         T = len(rows)
         if method in phaseMethods and T <= 16:
             # every trial's unit phasor weighs 2 / T >= 1 / 8 of the estimate: where a single-trial cross spectrum passes
@@ -350,20 +372,18 @@ class CrossSpectra(ComputationalRoutine):
             return True
         if freq_idx.size < 4:
             return False
-        pr = cfg["polyremoval"] if cfg["polyremoval"] in (0, 1) and cfg["polyremoval"] is not False else None
-        lo, hi = parallel.my_shard(T)
+        lo, hi = parallel.my_shard(T)                      # (not my_trials: the routine need not be initialised yet)
         mine = rows[lo:hi][:sample]
         looks = getattr(data, "_looks", None)
         key = (tuple(mine), None if chans is None else tuple(int(c) for c in chans), cfg["nSamples"], str(cfg["taper"]),
-               repr(sorted((cfg["taper_opt"] or {}).items())), bool(cfg["demean_taper"]), pr, freq_idx.tobytes(), T)
+               repr(sorted((cfg["taper_opt"] or {}).items())), bool(cfg["demean_taper"]), stream.polyremoval,
+               freq_idx.tobytes(), T)
         if looks is not None and key in looks:
             ratio, K = looks[key]
         else:
             ratio, K = 0.0, 1
             with hs.precision("float32"):
-                for _, spec in hs.run_mtmfft_batches(dev, mine, chans, cfg["nSamples"], cfg["taper"], cfg["taper_opt"],
-                                                     cfg["demean_taper"], False, pr, None, "pow", True, reuse=True,
-                                                     upload=upload):
+                for _, spec in stream.batches(mine, output="pow", whole_axis=True):
                     K = spec.shape[1]
                     ratio = max(ratio, hs.dynamic_range(spec, kept=freq_idx, few_products=T * K <= 16))   # whole axis: see hs.dynamic_range
             if looks is not None:
@@ -385,21 +405,13 @@ class CrossSpectra(ComputationalRoutine):
         'powcorr_ortho' (K12 on the same stream, every taper a repetition: backend.envelope_accumulator; its pair sums are
         float64, 1.07 GB at 256 channels x 2049 frequencies and 5.4 GB for 'powcorr_ortho').  Returns the (F, C, C) float32
         device tensor."""
-        cfg = self.cfg
-        dev = data.device_data()
-        rows, chans = device_rows(data), selected_channels(data)
-        nS = cfg["nSamples"] if cfg["nSamples"] is not None else rows[0][1] - rows[0][0]
-        freqs, freq_idx = _freq_selection(nS, cfg["samplerate"], cfg["foi"])
-        pr = cfg["polyremoval"] if cfg["polyremoval"] in (0, 1) and cfg["polyremoval"] is not False else None
-        F, C = self.targetShapes[0][1], self.targetShapes[0][2]
-        T = self.numTrials
-        mine = [rows[k] for k in self.my_trials()]
-        add, finish = _trial_stream_sums(measure, F, C, dev.device)
-        for _, spec in hs.run_mtmfft_batches(dev, mine, chans, cfg["nSamples"], cfg["taper"], cfg["taper_opt"],
-                                             cfg["demean_taper"], False, pr, freq_idx, "fourier", True, reuse=True):
+        stream = self._stream(data)
+        F, C = stream.F, stream.C
+        add, finish = _trial_stream_sums(measure, F, C, stream.dev.device)
+        for _, spec in stream.batches(stream.mine):
             add(spec.reshape(-1, F, C), spec.shape[1])
-        self.metadata = [{"freqs_hash": _freqs_hash(freqs)}] * T
-        return finish(T)
+        self.metadata = stream.metadata
+        return finish(stream.T)
 
     def jackknife_hip(self, data, evaluate, fused=None):
         """Streaming jackknife on the device (connectivity_analysis.py:601-606,736-757; statistics/jackknifing.py):
@@ -413,27 +425,15 @@ class CrossSpectra(ComputationalRoutine):
         `fused(spec, ntaper, S, direct, T, sum_d, sum_d2)`: optional single-kernel form of pass 2 for a batch of
         trials (NormalizeCrossSpectra.jackknife_accumulate)."""
         cfg = self.cfg
-        dev = data.device_data()
-        rows, chans = device_rows(data), selected_channels(data)
-        nS = cfg["nSamples"] if cfg["nSamples"] is not None else rows[0][1] - rows[0][0]
-        freqs, freq_idx = _freq_selection(nS, cfg["samplerate"], cfg["foi"])
-        pr = cfg["polyremoval"] if cfg["polyremoval"] in (0, 1) and cfg["polyremoval"] is not False else None
-        F, C = self.targetShapes[0][1], self.targetShapes[0][2]
-        T = self.numTrials
-        mine = [rows[k] for k in self.my_trials()]
-        args = (dev, chans, cfg["nSamples"], cfg["taper"], cfg["taper_opt"], cfg["demean_taper"], pr, freq_idx)
-
-        def batches(rr):
-            return hs.run_mtmfft_batches(args[0], rr, args[1], args[2], args[3], args[4], args[5], False, args[6],
-                                         args[7], "fourier", True, reuse=True)
-
+        stream = self._stream(data)
+        dev, mine, F, C, T = stream.dev, stream.mine, stream.F, stream.C, stream.T
         # ---- pass 1: trial average
         S = torch.zeros((F, C, C), dtype=torch.complex64, device=dev.device)
         K = 1
         if backend.trials_apart() and mine:
-            S, K = self._sum_trials_apart(batches(mine), F, C, dev.device)
+            S, K = self._sum_trials_apart(stream.batches(mine), F, C, dev.device)
         else:
-            for _, spec in batches(mine):
+            for _, spec in stream.batches(mine):
                 K = spec.spyhip_ntaper
                 backend.csd_accumulate(spec, S, absmax=getattr(spec, "spyhip_absmax", None))
         K = int(cfg["taper_opt"].get("Kmax", K)) if cfg["taper_opt"] else K
@@ -445,7 +445,7 @@ class CrossSpectra(ComputationalRoutine):
         sum_d = torch.zeros(direct.shape, dtype=torch.complex128 if cplx else torch.float64, device=dev.device)
         sum_d2 = torch.zeros(direct.shape, dtype=torch.float64, device=dev.device)
         St = None if fused is not None else torch.empty_like(S)
-        for _, spec in batches(mine):
+        for _, spec in stream.batches(mine):
             if fused is not None:
                 # the AV stage offers the whole pass 2 as one kernel (coherence: K9): replicates never exist in HBM
                 fused(spec.reshape(-1, F, C), spec.shape[1], S, direct, T, sum_d, sum_d2)
@@ -464,7 +464,7 @@ class CrossSpectra(ComputationalRoutine):
         bias = ((T - 1) * (sum_d / T)).to(direct.dtype)
         mag2 = (sum_d.real ** 2 + sum_d.imag ** 2) if cplx else sum_d * sum_d
         var = ((T - 1) * (sum_d2 - mag2 / T)).clamp_(min=0).to(torch.float32)
-        self.metadata = [{"freqs_hash": _freqs_hash(freqs)}] * T
+        self.metadata = stream.metadata
         return S, direct, bias, var
 
     def process_metadata(self, data, out):
@@ -491,10 +491,12 @@ def _padded_spectra(dev, rows, chans, n, polyremoval, max_bytes=8 << 30):
         yield spec.reshape(len(starts), L // 2 + 1, nchan)
 
 
-def _ccov_trials(dev, rows, chans, polyremoval, scale, norm):
-    """K8 on the trials `rows` (equal length): cross spectra of the zero-padded trials summed by the MFMA kernel,
-    one inverse transform per channel pair.  Returns ((nlag, C, C) float32 device tensor, raw accumulator)."""
-    n = rows[0][1] - rows[0][0]
+def _ccov_trials(dev, rows, chans, polyremoval, n=None):
+    """K8's input from the trials `rows` (equal length `n`; given where `rows` may be empty, a rank without trials): the
+    cross spectra of the zero-padded trials summed by the MFMA kernel.  Returns (raw accumulator (L/2 + 1, C, C) complex64
+    on the device, n) for backend.ccov_from_accumulator, which runs one inverse transform per channel pair."""
+    if n is None:
+        n = rows[0][1] - rows[0][0]
     L = backend.ccov_nfft(n)
     nchan = dev.shape[1] if chans is None else len(chans)
     acc = torch.zeros((L // 2 + 1, nchan, nchan), dtype=torch.complex64, device=dev.device)
@@ -515,8 +517,7 @@ def cross_covariance_cF(trl_dat, samplerate=1, polyremoval=0, timeAxis=0, norm=F
         return outShape, spectralDTypes["abs"]
     backend.require_gpu()
     dev = torch.from_numpy(np.ascontiguousarray(dat, dtype=np.float32)).cuda()
-    pr = polyremoval if polyremoval in (0, 1) and polyremoval is not False else None
-    acc, n = _ccov_trials(dev, [(0, nSamples)], None, pr, 1.0, norm)
+    acc, n = _ccov_trials(dev, [(0, nSamples)], None, _polyremoval(polyremoval))
     CC = backend.to_host(backend.ccov_from_accumulator(acc, n, 1.0, 2 if norm else 0))[:, np.newaxis]
     if fullOutput:
         return CC, np.arange(nlag) / samplerate
@@ -535,13 +536,13 @@ class CrossCovariance(ComputationalRoutine):
         cfg = self.cfg
         dev = data.device_data()
         rows, chans = device_rows(data), selected_channels(data)
-        pr = cfg["polyremoval"] if cfg["polyremoval"] in (0, 1) and cfg["polyremoval"] is not False else None
+        pr = _polyremoval(cfg["polyremoval"])
         T = self.numTrials
         mine = [rows[k] for k in self.my_trials()]
         if self.keeptrials:
             parts = []
             for r in mine:
-                acc, n = _ccov_trials(dev, [r], chans, pr, 1.0, cfg["norm"])
+                acc, n = _ccov_trials(dev, [r], chans, pr)
                 parts.append(backend.ccov_from_accumulator(acc, n, 1.0, 2 if cfg["norm"] else 0).unsqueeze(1))
             from ..specest.compRoutines import _store_trials
             _store_trials(self, out, parts)
@@ -549,12 +550,7 @@ class CrossCovariance(ComputationalRoutine):
         lens = {r[1] - r[0] for r in rows}
         if len(lens) != 1:
             raise ValueError("trial averaging of cross-covariances needs trials of equal length")
-        n = lens.pop()
-        L = backend.ccov_nfft(n)
-        nchan = self.targetShapes[0][2]
-        acc = torch.zeros((L // 2 + 1, nchan, nchan), dtype=torch.complex64, device=dev.device)
-        for spec in _padded_spectra(dev, mine, chans, n, pr):
-            backend.csd_accumulate(spec, acc)
+        acc, n = _ccov_trials(dev, mine, chans, pr, n=lens.pop())
         backend.csd_allreduce_(acc)
         res = backend.ccov_from_accumulator(acc, n, 1.0 / T, 2 if cfg["norm"] else 0)
         out._dev = res.unsqueeze(1)

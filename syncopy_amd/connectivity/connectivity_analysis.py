@@ -1,8 +1,7 @@
 """`connectivityanalysis` metafunction: method = 'csd' | 'coh' | 'granger' | 'ppc' | 'corr', and beyond the reference
-'plv' | 'pli' | 'wpli' | 'wpli_debiased', which behave as 'ppc' does throughout, 'dtf' | 'pdc', which take every rule
-of 'granger' (they are measures of the same Wilson factors), and the envelope correlations 'amplcorr' | 'powcorr' |
-'powcorr_ortho', which behave as 'ppc' does on the batched route and have no other, and the phase slope index 'psi', which
-takes every rule of 'coh' and its own keyword `bandwidth`.
+'plv' | 'pli' | 'wpli' | 'wpli_debiased', 'dtf' | 'pdc', the envelope correlations 'amplcorr' | 'powcorr' | 'powcorr_ortho'
+and the phase slope index 'psi' with its own keyword `bandwidth`.  Which rules a method takes - those of 'ppc', of
+'granger', of 'coh' - is one row of the table `_METHODS` below, which every function here reads.
 
 Two-stage pipeline of syncopy/connectivity/connectivity_analysis.py: single-trial
 cross-spectra accumulated over trials (ST stage, :587-599), then one evaluation on the
@@ -12,12 +11,15 @@ trial average (AV stage, :677-679).  Parameter handling follows :286-473 and the
 import functools
 import numbers
 import weakref
+from collections import namedtuple
+from contextlib import ExitStack
 
 import numpy as np
 
 from ..datatype import (AnalogData, CrossSpectralData, SpectralData, require_real_analog, selected_channels,
                         selected_trialdefinition)
-from ..shared.const_def import connectivity_outputs, connectivityMethods, directedMethods, envelopeMethods, phaseMethods
+from ..shared.const_def import (connectivity_outputs, connectivityMethods, directedMethods,
+                                envelopeMethods, phaseMethods)    # noqa: F401  (all three families stay importable from here)
 from ..shared.errors import SPYTypeError, SPYValueError, SPYWarning
 from ..shared.kwarg_decorators import attached_selection, unwrap_cfg
 from ..shared.input_processors import process_foi, process_padding, process_taper
@@ -25,6 +27,41 @@ from ..shared.tools import best_match
 from .AV_compRoutines import (NormalizeCrossCov, NormalizeCrossSpectra, PhaseSlope, pairwise_phase_consistency,
                               phase_lag)
 from .ST_compRoutines import CrossCovariance, CrossSpectra, SpectralDyadicProduct
+
+# What the front end knows of a method:
+#   av        the stage after the single-trial cross spectra: None (they are the result), "coh", "psi", "granger",
+#             "directed" (classes[method]), or "stream" - no second stage, the trials stream through `_ppc`
+#   averaged  `keeptrials` has to be False
+#   jackknife `jackknife=True` is honoured
+#   wilson    the rules of the Wilson factorisation hold: no `foi`, the channels-per-trial warning, tapers of zero mean,
+#             "not part of this build" without the kernels
+#   look      precision="auto": the branch of CrossSpectra.needs_float64 to ask, True for float64 transforms whatever
+#             the data, None where the question is never put
+#   cmb       `channelcmb` on SpectralData: "rect" forms the rectangular product, "post" selects from the full result,
+#             "pairwise" factorises every (sender, receiver) pair on its own
+#   batched   there is no per-trial route
+#   diag0     sender = receiver is exactly 0 (measures of the imaginary part alone)
+#   outputs   the legal values of `output`, where the method restricts them
+_Method = namedtuple("_Method", "av averaged jackknife wilson look cmb batched diag0 outputs",
+                     defaults=(None, False, False, False, None, None, False, False, None))
+_METHODS = {
+    "coh": _Method("coh", averaged=True, jackknife=True, look="coh", cmb="post", outputs=connectivity_outputs),
+    "corr": _Method(),
+    "csd": _Method(cmb="rect"),
+    "granger": _Method("granger", averaged=True, jackknife=True, wilson=True, look="granger", cmb="pairwise"),
+    "ppc": _Method("stream", averaged=True, look="ppc", cmb="rect"),
+    "plv": _Method("stream", averaged=True, look="plv", cmb="rect"),
+    "pli": _Method("stream", averaged=True, look="pli", cmb="rect", diag0=True),
+    "wpli": _Method("stream", averaged=True, look="wpli", cmb="rect", diag0=True),
+    "wpli_debiased": _Method("stream", averaged=True, look="wpli_debiased", cmb="rect", diag0=True),
+    "dtf": _Method("directed", averaged=True, wilson=True, look="granger", cmb="post", outputs=("abs", "pow")),
+    "pdc": _Method("directed", averaged=True, wilson=True, look="granger", cmb="post", outputs=("abs", "pow")),
+    "amplcorr": _Method("stream", averaged=True, look="ppc", cmb="rect", batched=True),
+    "powcorr": _Method("stream", averaged=True, look="ppc", cmb="rect", batched=True),
+    "powcorr_ortho": _Method("stream", averaged=True, look="ppc", cmb="rect", batched=True),
+    "psi": _Method("psi", averaged=True, jackknife=True, look=True, cmb="post"),
+}
+assert tuple(_METHODS) == connectivityMethods, "one row per method of shared.const_def.connectivityMethods, in its order"
 
 
 @unwrap_cfg
@@ -70,16 +107,17 @@ def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi
     if not isinstance(data, (AnalogData, SpectralData)) or data.data is None:
         raise SPYValueError("either AnalogData or SpectralData as input", "data", data.__class__.__name__)
     require_real_analog(data)
-    if method not in connectivityMethods:
+    if method not in connectivityMethods:            # (the tuple, not the table: an unhashable `method` is answered too)
         raise SPYValueError("one of " + ", ".join(connectivityMethods), varname="method", actual=method)
     if not isinstance(jackknife, bool):
         raise SPYTypeError(jackknife, "jackknife", "boolean")
-    if jackknife and method not in ("coh", "granger", "psi"):
+    rule = _METHODS[method]
+    if jackknife and not rule.jackknife:
         SPYWarning(f"Jackknife is not available for method {method}")       # connectivity_analysis.py:310-317
         jackknife = False
     if not isinstance(noise_weighted, bool):
         raise SPYTypeError(noise_weighted, "noise_weighted", "boolean")
-    if noise_weighted and method not in directedMethods:
+    if noise_weighted and rule.av != "directed":
         raise SPYValueError("False, noise weighting exists for the methods " + ", ".join(directedMethods) + " only",
                             varname="noise_weighted", actual=f"True with method {method}")
     if bandwidth is not None:
@@ -89,8 +127,8 @@ def connectivityanalysis(data, method="coh", keeptrials=False, output="abs", foi
         if (isinstance(bandwidth, (bool, np.bool_)) or not isinstance(bandwidth, numbers.Real) or not np.isfinite(bandwidth)
                 or bandwidth <= 0):
             raise SPYValueError("a positive number (Hz) or None", varname="bandwidth", actual=str(bandwidth))
-    if method in directedMethods and output not in ("abs", "pow"):
-        raise SPYValueError("'abs' or 'pow'", varname="output", actual=str(output))
+    if rule.av == "directed" and output not in rule.outputs:
+        raise SPYValueError(" or ".join(repr(o) for o in rule.outputs), varname="output", actual=str(output))
     if polyremoval is not None:
         if not isinstance(polyremoval, numbers.Number) or polyremoval not in (0, 1):
             raise SPYValueError("0, 1 or None", varname="polyremoval", actual=polyremoval)
@@ -244,33 +282,31 @@ def _connectivity_from_spectra(data, classes, method, keeptrials, output, comput
     if not np.issubdtype(np.asarray(data.data).dtype, np.complexfloating):
         raise SPYValueError("complex valued spectra, set `output='fourier'` in spy.freqanalysis!", "data",
                             "real valued spectral data")
-    if method == "granger" and data.data.shape[data.dimord.index("time")] != len(data.sampleinfo):
-        raise NotImplementedError("Time resolved Granger causality from tf-spectra not available atm")
-    if method in directedMethods and data.data.shape[data.dimord.index("time")] != len(data.sampleinfo):
-        raise NotImplementedError(f"Time resolved {method} from tf-spectra not available")
+    rule = _METHODS[method]
+    if rule.wilson and data.data.shape[data.dimord.index("time")] != len(data.sampleinfo):
+        raise NotImplementedError("Time resolved Granger causality from tf-spectra not available atm" if rule.av == "granger"
+                                  else f"Time resolved {method} from tf-spectra not available")
     log_dict = {"method": method, "output": output, "keeptrials": keeptrials}
-    if method == "psi":
+    if rule.av == "psi":
         log_dict.update(bandwidth=bandwidth, h=_psi_half(data.freq, bandwidth))
-    if cmb is not None and (method == "csd" or method in phaseMethods + envelopeMethods):
+    if cmb is not None and rule.cmb == "rect":
         # truly rectangular products (connectivity_analysis.py:503-529)
         st = classes["dyadic"](send_idx=cmb[0], send_N=len(cmb[0]), rec_idx=cmb[1], rec_N=len(cmb[1]))
     else:
         st = classes["dyadic"]()
-    if cmb is not None and method == "granger":
+    if cmb is not None and rule.cmb == "pairwise":
         if "granger" not in classes:
             raise NotImplementedError("Wilson/Granger kernels are not part of this build")
         if jackknife:
             SPYWarning("jackknife estimates are not computed for pairwise (channelcmb) Granger causality")
         return _pairwise_granger(data, classes, st, compute_method, log_dict, *cmb)
     out = _run_stages(data, classes, st, method, keeptrials, output, compute_method, jackknife, log_dict)
-    if cmb is not None and method in directedMethods:
-        # the multivariate measure, post-selected: conditioning on every channel is the point of these measures
+    if cmb is not None and rule.cmb == "post":
+        # (of a directed measure too: conditioning on every channel is the point of the multivariate measure)
         info = dict(out.info)
-        out = _post_select(out, *cmb)
-        out.info.update(info)
-    if cmb is not None and method in ("coh", "psi"):
         jack = {k: getattr(out, k, None) for k in ("jack_var", "jack_bias")}
         out = _post_select(out, *cmb)
+        out.info.update(info)
         for k, v in jack.items():
             if v is not None:
                 setattr(out, k, np.ascontiguousarray(np.asarray(v)[..., cmb[0], :][..., cmb[1]]))
@@ -313,10 +349,11 @@ def _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, p
     if nTrials == 1 and method != "corr":
         raise SPYValueError("multi-trial input data, spectral connectivity measures critically depend on trial "
                             "averaging!", "data", "only one trial")
-    if keeptrials is not False and method in ("coh", "granger", "psi") + phaseMethods + directedMethods + envelopeMethods:
+    rule = _METHODS[method]
+    if keeptrials is not False and rule.averaged:
         raise SPYValueError(f"False, trial averaging needed for method {method}!", varname="keeptrials",
                             actual=keeptrials)
-    if method in envelopeMethods and compute_method not in (None, "hip"):
+    if rule.batched and compute_method not in (None, "hip"):
         raise NotImplementedError(f"method {method} runs on the batched route only (compute_method=None or 'hip'): the "
                                   "per-trial engine keeps single-trial cross spectra, which are summed over the tapers "
                                   "and cannot give a correlation over the repetitions")
@@ -327,7 +364,7 @@ def _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, p
                                           bandwidth)
     nSamples = process_padding(pad, lenTrials, fs)
     foi, foilim = process_foi(foi, foilim, fs)
-    if method == "granger" or method in directedMethods:
+    if rule.wilson:
         if foi is not None or foilim is not None:
             raise SPYValueError("no foi specification for Granger analysis", "foi/foilim",
                                 "foi or foilim specification")
@@ -347,11 +384,11 @@ def _connectivity(data, classes, method, keeptrials, output, foi, foilim, pad, p
                                      samplerate=fs, nSamples=lenTrials.mean(), output="pow")
     log_dict = {"method": method, "output": output, "keeptrials": keeptrials, "polyremoval": polyremoval,
                 "pad": pad, "foi": foi, "taper": taper, "taper_opt": taper_opt}
-    if method == "psi":
+    if rule.av == "psi":
         log_dict.update(bandwidth=bandwidth, h=_psi_half(foi, bandwidth))
 
     st = classes["csd"](samplerate=fs, nSamples=nSamples, taper=taper, taper_opt=taper_opt,
-                        demean_taper=(method == "granger" or method in directedMethods), polyremoval=polyremoval, timeAxis=timeAxis, foi=foi)
+                        demean_taper=rule.wilson, polyremoval=polyremoval, timeAxis=timeAxis, foi=foi)
     return _run_stages(data, classes, st, method, keeptrials, output, compute_method, jackknife, log_dict)
 
 
@@ -385,7 +422,7 @@ def _ppc(data, classes, st, compute_method, log_dict, method="ppc"):
     correlation (envelopeMethods), which takes the first path with its own sums (K12) and has no second."""
     from .. import backend
     out = CrossSpectralData(dimord=CrossSpectra.dimord)
-    if method in envelopeMethods and not hasattr(st, "ppc_hip"):
+    if _METHODS[method].batched and not hasattr(st, "ppc_hip"):
         raise NotImplementedError(f"method {method} needs a single-trial routine with the batched route (ppc_hip)")
     if compute_method in (None, "hip") and hasattr(st, "ppc_hip"):
         st.initialize(data, out._stackingDim, chan_per_worker=None, keeptrials=False)
@@ -407,7 +444,7 @@ def _ppc(data, classes, st, compute_method, log_dict, method="ppc"):
         per_time = single.reshape((-1, L) + single.shape[1:])            # (trials, time, F, C_i, C_j)
         res = np.ascontiguousarray(np.concatenate([classes[method](per_time[:, ti]) for ti in range(L)], axis=0),
                                    dtype=np.float32)
-        if method in ("pli", "wpli", "wpli_debiased"):
+        if _METHODS[method].diag0:
             # sender = receiver: exactly 0, as the batched path's finalizer writes it (Im S_ii is a rounding residue at best)
             res[..., np.asarray(st_out.channel_i)[:, None] == np.asarray(st_out.channel_j)[None, :]] = 0.0
         out.data = res
@@ -418,98 +455,94 @@ def _ppc(data, classes, st, compute_method, log_dict, method="ppc"):
     return out
 
 
+def _av_routine(classes, method, output, log_dict):
+    """The AV routine of `method`, None where the trial-averaged cross spectra are the result."""
+    rule = _METHODS[method]
+    if rule.av == "coh":
+        if output not in rule.outputs:
+            raise SPYValueError(f"one of {sorted(rule.outputs)}", varname="output", actual=output)
+        return classes["coh"](output=output)
+    if rule.av == "psi":
+        return classes["psi"](half=log_dict["h"])
+    if rule.av == "granger":
+        if "granger" not in classes:
+            raise NotImplementedError("Wilson/Granger kernels are not part of this build")
+        return classes["granger"](rtol=5e-6, nIter=100, cond_max=1e4)
+    if rule.av == "directed":
+        if method not in classes:
+            raise NotImplementedError("Wilson/Granger kernels are not part of this build")
+        return classes[method](output=output, rtol=5e-6, nIter=100, cond_max=1e4)
+    return None
+
+
 def _run_stages(data, classes, st, method, keeptrials, output, compute_method, jackknife, log_dict):
     """ST stage (single-trial cross spectra, trial-averaged unless kept) -> AV stage, plus the jackknife.
     Coherence outputs that are the imaginary part or the phase run K4 with directly summed imaginary parts
     (backend.csd_phase_exact): the default 3-multiplication kernels subtract three rounded row sums there."""
-    from contextlib import ExitStack
+    from .. import backend
     from ..specest import hip_spectral as hs
+    rule = _METHODS[method]
     batched = compute_method in (None, "hip")
     with ExitStack() as stack:
         # precision="auto": float64 transforms when the OUTPUT isolates a part of the complex coherency (its imaginary or real
         # part, its phase: 1.5e-7 of the modulus is not small against a part that nearly vanishes - as freqanalysis decides for
         # its own outputs), or when the DATA ask for them (CrossSpectra.needs_float64)
-        if (batched and hs.requested_precision() is None
-                and method in ("coh", "granger", "psi") + phaseMethods + directedMethods + envelopeMethods
-                and isinstance(data, AnalogData)
-                and ((method == "coh" and output in ("imag", "angle", "real"))
-                     or method == "psi"        # sums of imaginary parts of coherency products: as coh with output="imag"
-                     or (hasattr(st, "needs_float64")
-                         and st.needs_float64(data, "granger" if method in directedMethods
-                                              else "ppc" if method in envelopeMethods else method)))):
+        if (batched and hs.requested_precision() is None and rule.look is not None and isinstance(data, AnalogData)
+                and ((rule.av == "coh" and output in ("imag", "angle", "real"))
+                     or rule.look is True         # psi, sums of imaginary parts of coherency products: as coh with output="imag"
+                     or (hasattr(st, "needs_float64") and st.needs_float64(data, rule.look)))):
             stack.enter_context(hs.soft_reference())
-        from .. import backend
-        if method == "psi" and batched:
+        if rule.av == "psi" and batched:
             # a small difference of unit-scale coherencies: every trial's cross spectrum on its own, the trials added in float64
             stack.enter_context(backend.csd_trials_apart(True))
         # (psi on either route: its AV stage is the device's whatever engine accumulates the cross spectra)
-        if method == "psi" or (method == "coh" and output in ("imag", "angle") and batched):
+        if rule.av == "psi" or (rule.av == "coh" and output in ("imag", "angle") and batched):
             stack.enter_context(backend.csd_phase_exact(True))
-        return _run_stages_impl(data, classes, st, method, keeptrials, output, compute_method, jackknife, log_dict)
-
-
-def _run_stages_impl(data, classes, st, method, keeptrials, output, compute_method, jackknife, log_dict):
-    if method in phaseMethods + envelopeMethods:
-        return _ppc(data, classes, st, compute_method, log_dict, method)
-    if method == "coh":
-        if output not in connectivity_outputs:
-            raise SPYValueError(f"one of {sorted(connectivity_outputs)}", varname="output", actual=output)
-        av = classes["coh"](output=output)
-    elif method == "psi":
-        av = classes["psi"](half=log_dict["h"])
-    elif method == "granger":
-        if "granger" not in classes:
-            raise NotImplementedError("Wilson/Granger kernels are not part of this build")
-        av = classes["granger"](rtol=5e-6, nIter=100, cond_max=1e4)
-    elif method in directedMethods:
-        if method not in classes:
-            raise NotImplementedError("Wilson/Granger kernels are not part of this build")
-        av = classes[method](output=output, rtol=5e-6, nIter=100, cond_max=1e4)
-    else:
-        av = None
-
-    st_out = CrossSpectralData(dimord=CrossSpectra.dimord)
-    if (jackknife and av is not None and compute_method in (None, "hip") and hasattr(st, "jackknife_hip")
-            and hasattr(av, "evaluate_device")):
-        return _jackknife_on_device(data, st, av, st_out, log_dict)
-    # single trials are needed for the jackknife (connectivity_analysis.py:589-590)
-    st.initialize(data, st_out._stackingDim, chan_per_worker=None, keeptrials=bool(keeptrials) or jackknife)
-    st.compute(data, st_out, parallel=False, log_dict=log_dict, method=compute_method)
-    if av is None:
-        return st_out
-    replicates = None
-    if jackknife:
-        # leave-one-out trial averages (statistics/jackknifing.py:14-108): (T * mean - trial) / (T - 1)
-        S = np.asarray(st_out.data)
-        T = S.shape[0]
-        mean = _trial_average(S)
-        rep = np.empty_like(S)
-        for t in range(T):
-            loo = T * mean - S[t]
-            loo /= T - 1
-            rep[t] = loo
-        replicates = _as_single_trials(st_out, rep)
-        st_out = _as_single_trials(st_out, mean[None])
-        st_out.trialdefinition = np.array([[0, 1.0, 0]])
-    out = CrossSpectralData(dimord=st_out.dimord)
-    av.initialize(st_out, out._stackingDim, chan_per_worker=None, keeptrials=False)
-    av.pre_check()
-    av.compute(st_out, out, parallel=False, log_dict=log_dict, method=compute_method)
-    if jackknife:
-        # the same AV routine on every replicate, then bias and variance (jackknifing.py:111-184)
-        jack_rep = CrossSpectralData(dimord=st_out.dimord)
-        av_rep = av.__class__(**av.cfg)
-        av_rep.initialize(replicates, jack_rep._stackingDim, chan_per_worker=None, keeptrials=True)
-        av_rep.compute(replicates, jack_rep, parallel=False, log_dict=log_dict, method=compute_method)
-        R = np.asarray(jack_rep.data)
-        T = R.shape[0]
-        direct = np.asarray(out.data)
-        jack_avg = _trial_average(R)[None]
-        prefac = (T - 1) + 0j if np.issubdtype(direct.dtype, np.complexfloating) else (T - 1)
-        out.jack_bias = (prefac * (jack_avg - direct)).astype(direct.dtype)
-        var = np.zeros(direct.shape, dtype=np.float32)
-        for t in range(T):
-            var += (np.abs(jack_avg - R[t])) ** 2
-        var *= T - 1
-        out.jack_var = var
-    return out
+        if rule.av == "stream":
+            return _ppc(data, classes, st, compute_method, log_dict, method)
+        av = _av_routine(classes, method, output, log_dict)
+        st_out = CrossSpectralData(dimord=CrossSpectra.dimord)
+        if (jackknife and av is not None and compute_method in (None, "hip") and hasattr(st, "jackknife_hip")
+                and hasattr(av, "evaluate_device")):
+            return _jackknife_on_device(data, st, av, st_out, log_dict)
+        # single trials are needed for the jackknife (connectivity_analysis.py:589-590)
+        st.initialize(data, st_out._stackingDim, chan_per_worker=None, keeptrials=bool(keeptrials) or jackknife)
+        st.compute(data, st_out, parallel=False, log_dict=log_dict, method=compute_method)
+        if av is None:
+            return st_out
+        replicates = None
+        if jackknife:
+            # leave-one-out trial averages (statistics/jackknifing.py:14-108): (T * mean - trial) / (T - 1)
+            S = np.asarray(st_out.data)
+            T = S.shape[0]
+            mean = _trial_average(S)
+            rep = np.empty_like(S)
+            for t in range(T):
+                loo = T * mean - S[t]
+                loo /= T - 1
+                rep[t] = loo
+            replicates = _as_single_trials(st_out, rep)
+            st_out = _as_single_trials(st_out, mean[None])
+            st_out.trialdefinition = np.array([[0, 1.0, 0]])
+        out = CrossSpectralData(dimord=st_out.dimord)
+        av.initialize(st_out, out._stackingDim, chan_per_worker=None, keeptrials=False)
+        av.pre_check()
+        av.compute(st_out, out, parallel=False, log_dict=log_dict, method=compute_method)
+        if jackknife:
+            # the same AV routine on every replicate, then bias and variance (jackknifing.py:111-184)
+            jack_rep = CrossSpectralData(dimord=st_out.dimord)
+            av_rep = av.__class__(**av.cfg)
+            av_rep.initialize(replicates, jack_rep._stackingDim, chan_per_worker=None, keeptrials=True)
+            av_rep.compute(replicates, jack_rep, parallel=False, log_dict=log_dict, method=compute_method)
+            R = np.asarray(jack_rep.data)
+            T = R.shape[0]
+            direct = np.asarray(out.data)
+            jack_avg = _trial_average(R)[None]
+            prefac = (T - 1) + 0j if np.issubdtype(direct.dtype, np.complexfloating) else (T - 1)
+            out.jack_bias = (prefac * (jack_avg - direct)).astype(direct.dtype)
+            var = np.zeros(direct.shape, dtype=np.float32)
+            for t in range(T):
+                var += (np.abs(jack_avg - R[t])) ** 2
+            var *= T - 1
+            out.jack_var = var
+        return out

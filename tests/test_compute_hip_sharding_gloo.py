@@ -2,7 +2,8 @@
 classes (not the oracle-bound ones) run their real `compute_hip` in two and three gloo ranks with the device
 primitives replaced by CPU stand-ins (FFT through the oracle, the accumulation as an einsum, the collective through
 gloo), so the index math - which rows each rank transforms, which accumulator they land in, the ONE sum over ranks and
-the division by the GLOBAL trial and taper count - is what is tested, not the kernels."""
+the division by the GLOBAL trial and taper count - is what is tested, not the kernels.  `ppc_hip` and `jackknife_hip`, which
+read the same trial stream, run through the same stand-ins."""
 import os
 import socket
 
@@ -75,13 +76,56 @@ def _patch():
     def csd_allreduce_(acc):
         return parallel.allreduce_sum_(acc)
 
+    def ppc_accumulate(spec, ntaper, acc):
+        # the unit phasor of each trial's taper-averaged cross spectrum, summed over the trials
+        s = spec.reshape(-1, ntaper, spec.shape[-2], spec.shape[-1]).to(torch.complex128)
+        acc += _phasor_sum(torch.einsum("bkfi,bkfj->bfij", s, s.conj()) / ntaper).to(acc.dtype)
+        return acc
+
+    def ppc_finalize(acc, ntrials, lower_only=False):
+        return _ppc_of_sum(acc, ntrials).to(torch.float32)
+
     AnalogData.device_data = device_data
     AnalogData.upload_in_flight = lambda self: None
     hs.run_mtmfft_batches = run_mtmfft_batches
     backend.csd_accumulate, backend.csd_finalize, backend.csd_allreduce_ = csd_accumulate, csd_finalize, csd_allreduce_
+    backend.ppc_accumulate, backend.ppc_finalize = ppc_accumulate, ppc_finalize
     backend.require_gpu = lambda: None
     backend.to_host = lambda t: t.cpu().numpy()
     return calls
+
+
+def _phasor_sum(csd):
+    return (csd / csd.abs()).sum(dim=0)
+
+
+def _ppc_of_sum(U, T):
+    return (U.abs().to(torch.float64) ** 2 - T) / (T * (T - 1))
+
+
+def _coh_abs(csd):
+    """A plain coherence modulus (F, C, C) in float64: the `evaluate` of the jackknife."""
+    c = csd.to(torch.complex128)
+    p = torch.diagonal(c, dim1=-2, dim2=-1).real
+    return c.abs() / torch.sqrt(p[:, :, None] * p[:, None, :])
+
+
+def _stream_stage(which):
+    """CrossSpectra.ppc_hip or .jackknife_hip through the stand-ins: (results, rows this rank transformed - in the
+    recording's coordinates, in the order of the calls -, this rank's trials)."""
+    from syncopy_amd.connectivity.ST_compRoutines import CrossSpectra
+    from syncopy_amd.datatype import CrossSpectralData
+    calls = _patch()
+    data = _data()
+    st = CrossSpectra(samplerate=200.0, nSamples=None, foi=None, taper="dpss", taper_opt={"NW": 3.0, "Kmax": 5},
+                      demean_taper=False, polyremoval=0, timeAxis=0)
+    st.initialize(data, CrossSpectralData(dimord=CrossSpectra.dimord)._stackingDim, chan_per_worker=None, keeptrials=False)
+    if which == "ppc":
+        vals = [st.ppc_hip(data)]
+    else:
+        vals = st.jackknife_hip(data, _coh_abs, fused=None)
+    o = data._row_origin
+    return [v.numpy() for v in vals], [(a + o, b + o) for a, b in calls["rows"]], list(st.my_trials())
 
 
 def _st_stage(keeptrials):
@@ -113,6 +157,10 @@ def _worker(rank, world, port, tmp):
             res[f"rows{int(kt)}"] = np.array(rows)
             res[f"mine{int(kt)}"] = np.array(mine)
             res["all_rows"] = np.array(all_rows)
+        for which, names in (("ppc", ("ppc",)), ("jack", ("S", "direct", "bias", "var"))):
+            vals, rows, mine = _stream_stage(which)
+            res.update({f"{which}_{n}": v for n, v in zip(names, vals)})
+            res[f"{which}_rows"], res[f"{which}_mine"] = np.array(rows), np.array(mine)
         np.savez(os.path.join(tmp, f"rank{rank}.npz"), **res)
     finally:
         dist.destroy_process_group()
@@ -129,10 +177,26 @@ def _reference(keeptrials):
     return out if keeptrials else out.mean(axis=0, keepdims=True)
 
 
-@pytest.mark.parametrize("world", [2, 3])
-def test_compute_hip_shards_trials_and_sums_once(tmp_path, world):
-    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
-    z = [np.load(tmp_path / f"rank{r}.npz") for r in range(world)]
+def _trial_csds():
+    """Every trial's taper-averaged cross spectrum from the oracle's spectra, (T, F, C, C) complex128."""
+    out = []
+    for trl in _data().trials:
+        s, _ = O.mtmfft(O.detrend(np.array(trl), 0), 200.0, None, "dpss", {"NW": 3.0, "Kmax": 5})
+        s = torch.from_numpy(s).to(torch.complex128)
+        out.append(torch.einsum("kfi,kfj->fij", s, s.conj()) / s.shape[0])
+    return torch.stack(out)
+
+
+@pytest.fixture(scope="module", params=[2, 3])
+def ranks(request, tmp_path_factory):
+    """What every rank of a `world` of 2 and of 3 saved (one spawn per world for all tests of the module)."""
+    world, tmp = request.param, tmp_path_factory.mktemp("ranks")
+    mp.spawn(_worker, args=(world, _free_port(), str(tmp)), nprocs=world, join=True)
+    return [np.load(tmp / f"rank{r}.npz") for r in range(world)]
+
+
+def test_compute_hip_shards_trials_and_sums_once(ranks):
+    z, world = ranks, len(ranks)
     all_rows = [tuple(r) for r in z[0]["all_rows"]]
     for kt in (0, 1):
         # contiguous, disjoint shards in rank order that cover every trial exactly once - and each rank transformed
@@ -187,3 +251,35 @@ def test_precision_look_with_an_empty_shard(tmp_path):
     z = [np.load(tmp_path / f"peak{r}.npz") for r in range(world)]
     assert all(bool(x["ans"]) for x in z), "every rank takes the same (float64) branch"
     assert all(float(x["total"][0]) == world for x in z)
+
+
+def test_ppc_and_jackknife_stream_their_own_shard(ranks):
+    """ppc_hip and jackknife_hip under a process group: every rank transforms the rows of its own shard (once, and once
+    per pass), every rank ends with the same result, and that result is the formula on all trials in one process."""
+    z, world = ranks, len(ranks)
+    all_rows = [tuple(r) for r in z[0]["all_rows"]]
+    T = len(all_rows)
+    for which, passes in (("ppc", 1), ("jack", 2)):
+        mine = [list(z[r][f"{which}_mine"]) for r in range(world)]
+        assert sum(mine, []) == list(range(T))
+        for r in range(world):
+            assert [tuple(x) for x in z[r][f"{which}_rows"]] == [all_rows[k] for k in mine[r]] * passes
+    S_t = _trial_csds()
+    ref = {"ppc_ppc": _ppc_of_sum(_phasor_sum(S_t), T).to(torch.float32)}
+    # the jackknife of the docstring: d_t = replicate_t - direct, bias = (T-1) mean d_t, var = (T-1) (sum |d_t|^2 - |sum d_t|^2 / T),
+    # the leave-one-out average in complex64 and in the routine's operation order
+    S = S_t.mean(dim=0).to(torch.complex64)
+    direct = _coh_abs(S)
+    d = []
+    for t in range(T):
+        loo = T * S - S_t[t].to(torch.complex64)
+        loo /= T - 1
+        d.append(_coh_abs(loo) - direct)
+    d = torch.stack(d)
+    ref.update(jack_S=S, jack_direct=direct, jack_bias=(T - 1) * d.mean(dim=0),
+               jack_var=((T - 1) * ((d * d).sum(dim=0) - d.sum(dim=0) ** 2 / T)).clamp_(min=0).to(torch.float32))
+    for name, want in ref.items():
+        for r in range(world):
+            assert z[r][name].dtype == want.numpy().dtype and z[r][name].shape == tuple(want.shape)
+            assert_parity(z[r][name], want.numpy(), what=f"rank {r} of {world}: {name}")
+            assert np.array_equal(z[r][name], z[0][name])                          # every rank holds the same result

@@ -392,7 +392,7 @@ def test_ccov_vs_oracle(be, C, N, T, pr):
     ref = np.mean([O.cross_covariance(t, 1.0, pr, False)[0] for t in x], axis=0)[:, 0]
     dev = torch.from_numpy(x.reshape(T * N, C)).cuda()
     rows = [(t * N, (t + 1) * N) for t in range(T)]
-    acc, n = ST._ccov_trials(dev, rows, None, pr, 1.0, False)
+    acc, n = ST._ccov_trials(dev, rows, None, pr)
     got = be.ccov_from_accumulator(acc, N, 1.0 / T, 0).cpu().numpy()
     assert got.shape == ref.shape
     assert_parity(got, ref.astype(np.float32), what="ccov", atol_rel=1e-5)
@@ -400,7 +400,7 @@ def test_ccov_vs_oracle(be, C, N, T, pr):
                   O.normalize_ccov(ref[:, None])[:, 0].astype(np.float32), what="ccov normalised", atol_rel=1e-5)
     assert_parity(be.ccov_normalize_(torch.from_numpy(got).cuda()).cpu().numpy(),
                   O.normalize_ccov(ref[:, None])[:, 0].astype(np.float32), what="ccov_normalize", atol_rel=1e-5)
-    acc1, _ = ST._ccov_trials(dev, rows[:1], None, pr, 1.0, True)
+    acc1, _ = ST._ccov_trials(dev, rows[:1], None, pr)
     ref1 = O.cross_covariance(x[0], 1.0, pr, True)[0][:, 0]
     assert_parity(be.ccov_from_accumulator(acc1, N, 1.0, 2).cpu().numpy(), ref1.astype(np.float32),
                   what="single-trial cross-correlation (np.std products)", atol_rel=1e-5)

@@ -63,7 +63,7 @@ if "corr" in which:
     state = {}
 
     def accumulate():
-        state["acc"], _ = ST._ccov_trials(data, rows, None, 0, 1.0, False)
+        state["acc"], _ = ST._ccov_trials(data, rows, None, 0)
     dt_acc = sync_time(accumulate, n=2)
     dt_lag = sync_time(lambda: be.ccov_from_accumulator(state["acc"], N, 1.0 / T, 1), n=3)
     res["corr"] = {"accumulate_us_per_trial": 1e6 * dt_acc / T, "lags_ms": 1e3 * dt_lag,
